@@ -6,16 +6,21 @@ bf16): one step = the dynamic distortion of a clean 64x64x3 uint8 batch
 (14:31-64, draws and pixels on device) + ToTensor of both images
 (14:199-202), ResUNet forward, loss = L1 + 0.1 * VGG16-features[:16]
 perceptual (14:238-242), full backward, AdamW(lr 2e-4, wd 1e-4) (14:222,
-245).  Synthetic GTSRB-shaped clean images generated on device.  --repeats
-windows of --steps timed steps each; the median window is reported (SURVEY
-§8d: 10 warm-up + 50 timed steps, median of 3).
+245).  Synthetic GTSRB-shaped clean images generated on device.  A plain run
+sets up, warms up, times --steps steps in one window and prints the result
+line; --dump-outputs DIR also writes what the last timed step computed (loss,
+restored batch, updated parameters) as DIR/<name>.npy.  --full is the whole
+protocol: --repeats (3) windows of --steps timed steps each with the median
+window reported (10 warm-up + 50 timed steps, median of 3), the
+roofline probe and the CPU baseline.
 With --gpus N every rank runs the same per-GPU batch and gradients are
 all-reduced over RCCL (weak scaling).  Launched by torch.distributed.run
 (WORLD_SIZE set) it is one rank; run directly (``python bench.py --gpus 8``)
 it starts the N ranks itself through torch.distributed.run and exits with
 their status; a WORLD_SIZE that disagrees with --gpus is an error.
 
-Prints ONE JSON line on rank 0 with the driver's fields plus
+Prints ONE JSON line on rank 0 with the driver's fields plus, with --full
+(null in a plain run),
   roofline     -- the dominant kernel's algorithmic FLOP rate vs the MFMA peak,
                   timed with HIP events on the launch stream over eager steps
                   run right after the timed windows;
@@ -53,13 +58,20 @@ HBM_PEAK_GBS = 8000.0                           # HBM3E (MI355X_MICROARCH.md)
 MFMA_CEILING = 1995.9
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="timed windows of --steps steps each; the median window is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed windows of --steps steps each; the median window is reported "
+                         "(default: 1, so --steps is the number of timed steps; 3 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole protocol: 3 timed windows, the per-kernel roofline probe "
+                         "(eager steps after the timed region) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed "
+                         "(loss, restored batch sample, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=512, help="per-GPU batch")
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
@@ -71,7 +83,13 @@ def parse():
                     help="capture the step in a HIP graph and replay it (1/0; default: on)")
     ap.add_argument("--probe-steps", type=int, default=3,
                     help="eager steps timed per kernel for the roofline in graph mode")
-    return ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
+    if not a.full:
+        # a plain run does only what the headline figure needs
+        a.no_probe = a.no_cpu_baseline = True
+    return a
 
 
 def algorithmic_bytes(tag):
@@ -253,6 +271,30 @@ def launch_plan(gpus, argv, env):
             "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """Write ``arrays`` ({name: tensor}) as path/<name>.npy in float32.  The
+    files together stay under DUMP_BUDGET_BYTES: an array over its share of
+    the budget is cut to a fixed sample (indices drawn once from a seeded
+    generator that depends only on the array's size, sorted), so two builds
+    run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4 - 64 * len(arrays)        # elements; room for the .npy headers
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        v = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        share = left // (len(todo) - i)                       # small arrays leave room for large ones
+        if v.numel() > share:
+            g = torch.Generator().manual_seed(v.numel())
+            idx = torch.randperm(v.numel(), generator=g)[:share].sort().values
+            v = v.reshape(-1)[idx]
+        left -= v.numel()
+        np.save(os.path.join(path, name + ".npy"), v.numpy())
+
+
 def main():
     a = parse()
     # --gpus N without an outer launcher: start the N ranks here, before this
@@ -295,7 +337,7 @@ def main():
     model.train()
     perc = rr.VGGPerceptualLoss().to(dev)
     perc.compute_dtype = dt
-    flatten_parameters(model)
+    flat_params = flatten_parameters(model)
     dp = DataParallel(model, force_comm=dp1) if world > 1 or dp1 else None
     gscale = dp.grad_scale if dp else 1.0
     # the HIP graph needs graph-capturable collectives: RcclComm (any N on
@@ -328,6 +370,10 @@ def main():
     # RR_WEIGHT_PREFETCH=0)
     wprefetch = os.environ.get("RR_WEIGHT_PREFETCH", "1") != "0"
 
+    # --dump-outputs: the restored batch of the latest step (in a HIP graph:
+    # the captured step's output tensor, rewritten by every replay)
+    kept = {}
+
     def step():
         if wprefetch:
             model.prefetch_weights()
@@ -337,6 +383,8 @@ def main():
         bad = to_tensor(distort(clean_u8))
         opt.zero_grad(set_to_none=True)
         out = model(bad)
+        if a.dump_outputs:
+            kept["restored"] = out.detach()
         loss = rr.unified_loss(out, clean, perc, w_perc, grad_scale=gscale)
         loss.backward()
         opt.step()
@@ -408,6 +456,12 @@ def main():
     el = sorted(windows)[len(windows) // 2]          # median window (max over ranks)
     if graph is not None:
         loss = loss_g
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed step receives from its last run: the
+        # loss, the restored batch and the updated parameters (written before
+        # the probe's eager steps move the parameters on)
+        dump_outputs(a.dump_outputs, {"loss": loss, "restored": kept["restored"],
+                                      "params": flat_params})
     if not a.no_probe:
         # kernel durations for the roofline: the same kernels, timed eagerly
         # (every rank runs these steps: the backward's all-reduces pair up)

@@ -53,6 +53,45 @@ def test_self_launch_maps_ranks(tmp_path):
         assert g["argv"] == ["--gpus", "2", "--steps", "3"]
 
 
+def test_plain_run_is_lean_and_full_keeps_the_protocol():
+    """A plain run times one window of --steps steps and skips the probe and
+    the CPU baseline; --full restores the 3-window protocol with both, and
+    the explicit switches still hold there."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.repeats) == (7, 2, 1)
+    assert a.no_probe and a.no_cpu_baseline and a.dump_outputs is None
+    f = bench.parse(["--full"])
+    assert f.repeats == 3 and not f.no_probe and not f.no_cpu_baseline
+    f = bench.parse(["--full", "--no-probe", "--repeats", "2"])
+    assert f.repeats == 2 and f.no_probe and not f.no_cpu_baseline
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole, an array over its share cut to a
+    fixed sample (the same indices on every run), every file float32, the
+    files together within the budget."""
+    import numpy as np
+    import torch
+    import bench
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    big = torch.arange(5000, dtype=torch.float64).reshape(50, 100)
+    arrays = {"loss": torch.tensor(1.5, dtype=torch.bfloat16), "big": big,
+              "small": torch.arange(6, dtype=torch.float32).reshape(2, 3)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].shape == () and got["loss"] == 1.5
+    assert np.array_equal(got["small"], arrays["small"].numpy())
+    s = got["big"]
+    assert s.ndim == 1 and 500 < s.size < 5000 and np.all(np.diff(s) > 0)      # distinct elements of big
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 4096
+
+
 def test_roofline_traffic_reads_the_newest_pmc_summary():
     """roofline.traffic comes from the newest committed PMC summary: run tags
     order by round, then by letters (r4q after r3aq, r3aa after r3z)."""

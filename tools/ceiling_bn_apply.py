@@ -53,7 +53,7 @@ def child(mode):
             return dict(dt0=gm, dgamma0=dg0, dbeta0=db0, dalpha=dal)
         engine.ops.bn_backward_rows = no_apply
     import bench
-    sys.argv = ["bench.py", "--no-cpu-baseline", "--no-probe", "--steps", "30"]
+    sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-probe", "--steps", "30"]
     bench.main()
 
 

@@ -8,7 +8,7 @@
 #   tests            python -m pytest tests -m gpu (all)       -> <tag>_gpu_tests.log
 #   tests:<expr>     the same with -k <expr>
 #   smoke            __graft_entry__.smoke()                    -> <tag>_smoke.log
-#   bench            python bench.py (default protocol)         -> <tag>_bench.json
+#   bench            python bench.py --full (whole protocol)    -> <tag>_bench.json
 #   prof             tools/profile_round.sh <tag> (kernel stats, FETCH/WRITE, MFMA busy)
 #   inf              cfg5 at its stated config: --images 8192, fp32 and bf16
 #                                                               -> <tag>_inference_cfg5_{fp32,bf16}.json
@@ -46,7 +46,7 @@ run_step() {
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1
       local rc=$?; tail -2 ${O}_smoke.log; return $rc ;;
     bench)
-      timeout -k 10 400 python bench.py > ${O}_bench.json 2> ${O}_bench.err
+      timeout -k 10 400 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err
       local rc=$?; head -c 600 ${O}_bench.json; echo; return $rc ;;
     prof)
       timeout -k 10 1000 bash tools/profile_round.sh $TAG > ${O}_prof.log 2>&1
@@ -68,7 +68,7 @@ run_step() {
       local name=${arg%%=*} vals=${arg#*=}
       for i in 1 2 3; do
         for v in ${vals//,/ }; do
-          env $name=$v timeout -k 10 150 python bench.py --no-cpu-baseline --no-probe --steps 30 \
+          env $name=$v timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-probe --steps 30 \
             > ${O}_ab.log 2>&1 || return 1
           tail -1 ${O}_ab.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name=$v', d['value'], d['ms_per_step'])" >> ${O}_abstep.txt
         done
@@ -78,7 +78,7 @@ run_step() {
       for i in 1 2 3; do
         for L in cur other; do
           if [ $L = other ]; then export RR_LIB_PATH=$arg; else unset RR_LIB_PATH; fi
-          timeout -k 10 150 python bench.py --no-cpu-baseline --no-probe --steps 30 > ${O}_ab.log 2>&1 || return 1
+          timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-probe --steps 30 > ${O}_ab.log 2>&1 || return 1
           tail -1 ${O}_ab.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$L', d['value'], d['ms_per_step'])" >> ${O}_ablibs.txt
         done
       done
