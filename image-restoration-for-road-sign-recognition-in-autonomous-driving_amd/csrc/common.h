@@ -160,25 +160,63 @@ __device__ __forceinline__ float wave_sum(float v) {
   } while (0)
 
 // Kernel-path overrides for the parity tests, the library's one run-time
-// knob: RR_PATH="key=value[,key=value...]" (read per call).  Every default is
-// the measured-best path; the tests force a family off (conv3r=0,
-// stream3=0, stream1=0, swgrad=0, igemm_halo=0, wgrad_halo=0, ...) or a
-// workgroup kind (conv3r_wg=4/8, conv3r_segwg=4/8, conv3r_w64=0) to check
-// one shipped kernel against another on the same shape.  Unknown keys are
-// ignored; an unset variable costs one getenv.
-static inline int rr_path(const char *key, int dflt) {
+// knob: RR_PATH="key=value[,key=value...]".  Every default is the
+// measured-best path; the tests force a family off (conv3r=0, stream3=0,
+// stream1=0, swgrad=0, igemm_halo=0, wgrad_halo=0, ...) or a workgroup kind
+// (conv3r_wg=4/8, conv3r_segwg=4/8, conv3r_w64=0) to check one shipped kernel
+// against another on the same shape.
+// Every extern "C" entry point that routes reads the variable once, at its
+// top (rr_path_read: one getenv, one scan), and hands the snapshot down; no
+// function below the entry points looks at the environment.
+// Grammar (the same as roadrestore._lib.path_flag): items are separated by
+// ','; spaces around key and value are ignored; the value is an optional sign
+// and 1-9 decimal digits.  An item that is not that, and an unknown key, is
+// ignored (the default holds); the first valid item of a key wins.
+struct RrPath {
+  int stream3 = 1, stream3_strips = 1, stream1 = 1, stream1_minp = 131072;
+  int conv3r = 1, conv3r_w64 = 1, conv3r_wg = 0, conv3r_segwg = 0;
+  int igemm_halo = 1, swgrad = 1, wgrad_halo = 1, blur_tiled = 1;
+};
+
+static inline RrPath rr_path_read() {
+  RrPath r;
   const char *e = getenv("RR_PATH");
-  if (!e || !*e) return dflt;
-  const size_t kl = __builtin_strlen(key);
+  if (!e || !*e) return r;
+  static const struct { const char *key; int RrPath::*field; } keys[] = {
+      {"stream3", &RrPath::stream3}, {"stream3_strips", &RrPath::stream3_strips},
+      {"stream1", &RrPath::stream1}, {"stream1_minp", &RrPath::stream1_minp},
+      {"conv3r", &RrPath::conv3r}, {"conv3r_w64", &RrPath::conv3r_w64},
+      {"conv3r_wg", &RrPath::conv3r_wg}, {"conv3r_segwg", &RrPath::conv3r_segwg},
+      {"igemm_halo", &RrPath::igemm_halo}, {"swgrad", &RrPath::swgrad},
+      {"wgrad_halo", &RrPath::wgrad_halo}, {"blur_tiled", &RrPath::blur_tiled}};
+  unsigned seen = 0;
   for (const char *p = e; *p;) {
     const char *q = p;
     while (*q && *q != ',') ++q;
     const char *eq = p;
     while (eq < q && *eq != '=') ++eq;
-    if (eq < q && (size_t)(eq - p) == kl && __builtin_memcmp(p, key, kl) == 0) return atoi(eq + 1);
+    const char *k0 = p, *k1 = eq, *v0 = eq < q ? eq + 1 : q, *v1 = q;
+    while (k0 < k1 && *k0 == ' ') ++k0;
+    while (k1 > k0 && k1[-1] == ' ') --k1;
+    while (v0 < v1 && *v0 == ' ') ++v0;
+    while (v1 > v0 && v1[-1] == ' ') --v1;
+    const bool neg = v0 < v1 && *v0 == '-';
+    if (v0 < v1 && (*v0 == '-' || *v0 == '+')) ++v0;
+    int val = 0;
+    bool ok = eq < q && v1 > v0 && v1 - v0 <= 9;
+    for (const char *c = v0; ok && c < v1; ++c) {
+      ok = *c >= '0' && *c <= '9';
+      val = val * 10 + (*c - '0');
+    }
+    for (unsigned i = 0; ok && i < sizeof keys / sizeof keys[0]; ++i) {
+      const size_t kl = __builtin_strlen(keys[i].key);
+      if ((size_t)(k1 - k0) != kl || __builtin_memcmp(k0, keys[i].key, kl) != 0) continue;
+      if (!(seen >> i & 1)) r.*keys[i].field = neg ? -val : val;
+      seen |= 1u << i;
+    }
     p = *q ? q + 1 : q;
   }
-  return dflt;
+  return r;
 }
 
 static inline int rr_grid_cap(long long want, int cap = 2048) {

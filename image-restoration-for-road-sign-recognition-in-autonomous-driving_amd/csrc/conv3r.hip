@@ -45,7 +45,8 @@
 // Workgroup: 8 waves = WC channel groups x WP pixel groups; BC = 64 NW
 // channels per wave group.  Geometry per (W, BC) in R3 below.
 #include "common.h"
-#include "conv3r.h"
+#include "igemm_epi.h"
+#include "route.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -846,7 +847,6 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3r_kernel(IgemmArgs a) 
 // 64 wave tiles, except where that leaves fewer than 256 workgroups (one per
 // CU): the 8x8 256-channel layers (B = 512: 128 tiles) take 128 x 32 wave
 // tiles.  sg > 0: row-segment tiles (any H x W)
-struct R3Pick { int bc, nw, nwv, hb, sg; };
 int r3_tpx(R3Pick k) { return (k.nwv / (k.bc / k.nw)) * 128; }
 
 // square 8 / 16 / 32 / 64 maps whose pixel count fills whole tiles take the
@@ -864,12 +864,12 @@ int r3_tpx(R3Pick k) { return (k.nwv / (k.bc / k.nw)) * 128; }
 // (RR_PATH, common.h): conv3r_wg=4 / 8 forces a workgroup kind,
 // conv3r_w64=0 puts the 64x64 maps on row-segment tiles, conv3r_segwg=4 / 8
 // the row-segment workgroup kind
-R3Pick r3_pick(const rr_igemm_desc *d) {
+R3Pick r3_pick(const rr_igemm_desc *d, const RrPath &p) {
   const long long P = (long long)d->n * d->h * d->w;
   const int W = d->w;
-  const bool w64 = W == 64 && rr_path("conv3r_w64", 1) != 0;
+  const bool w64 = W == 64 && p.conv3r_w64 != 0;
   const bool square = d->h == W && (W == 8 || W == 16 || W == 32 || w64);
-  const int fwg = rr_path("conv3r_wg", 0);
+  const int fwg = p.conv3r_wg;
   const int nwv = fwg == 4 || fwg == 8 ? fwg : (d->c_out % 128 == 0 && W != 32 ? 8 : 4);
   if (square) {
     R3Pick c[3];
@@ -909,7 +909,7 @@ R3Pick r3_pick(const rr_igemm_desc *d) {
   // W <= 28 (the 28x28 / 14x14 layers: 9-12 % faster), 2 x 4-wave elsewhere
   // (the 224 / 112 / 56 layers: even or 5-10 % slower,
   // profiles/r3v_ab224_segwg.jsonl)
-  const int fsw = rr_path("conv3r_segwg", 0);
+  const int fsw = p.conv3r_segwg;
   const int segwg = fsw == 4 || fsw == 8 ? fsw : (d->c_out % 128 == 0 && W <= 28 ? 8 : 4);
   if (segwg == 8) {
     if (sg == 2) return d->c_out % 128 == 0 ? R3Pick{128, 64, 8, 2, 2} : R3Pick{64, 32, 8, 2, 2};
@@ -934,23 +934,20 @@ long long r3_ptiles(const rr_igemm_desc *d, R3Pick k) {
 
 // RR_PATH conv3r=0: the halo / tiled kernels instead (tests), conv3r=2:
 // whole-row tiles only
-int conv3r_bc(const rr_igemm_desc *d) {
-  const int mode = rr_path("conv3r", 1);
-  if (mode == 0) return 0;
-  if (!d || d->dtype != RR_BF16 || d->mode != RR_CONV3X3 || d->out_nchw) return 0;
+int conv3r_bc(const rr_igemm_desc *d, const RrPath &p, R3Pick *k) {
+  if (p.conv3r == 0) return 0;
+  if (d->dtype != RR_BF16 || d->mode != RR_CONV3X3 || d->out_nchw) return 0;
   if (d->n <= 0 || d->h <= 0 || d->w <= 0) return 0;
   if (d->c_in1 <= 0 || d->c_in1 % 32 || d->c_in2 % 32 || d->c_out % 64) return 0;
   if (d->out_split && (d->out_split % 32 || d->out_split >= d->c_out)) return 0;
-  const R3Pick k = r3_pick(d);
-  if (k.sg && mode == 2) return 0;
-  const long long tiles = r3_ptiles(d, k) * (d->c_out / k.bc);
+  *k = r3_pick(d, p);
+  if (k->sg && p.conv3r == 2) return 0;
+  const long long tiles = r3_ptiles(d, *k) * (d->c_out / k->bc);
   if (tiles <= 0 || tiles > 0x7fffffffLL) return 0;
-  return k.bc;
+  return k->bc;
 }
 
-int conv3r_stat_blocks(const rr_igemm_desc *d) {
-  if (!conv3r_bc(d)) return 0;
-  const R3Pick k = r3_pick(d);
+int conv3r_rows(const rr_igemm_desc *d, R3Pick k) {
   return (int)(r3_ptiles(d, k) * (k.nwv / (k.bc / k.nw)));   // one row per wave row of a tile
 }
 
@@ -1008,9 +1005,7 @@ static int conv3r_go(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
   return RR_OK;
 }
 
-int conv3r_launch(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
-  if (!conv3r_bc(d)) return RR_EUNSUPPORTED;
-  const R3Pick k = r3_pick(d);
+int conv3r_launch(const rr_igemm_desc *d, IgemmArgs &a, R3Pick k, hipStream_t st) {
   if (k.sg == 2) {
     if (k.nwv == 8) {
       if (k.bc == 128) return conv3r_go<128, 64, 8, 2, 2>(d, a, st);
@@ -1038,29 +1033,19 @@ int conv3r_launch(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
   return conv3r_go<64, 32, 4, 1, 0>(d, a, st);
 }
 
-const char *conv3r_name(const rr_igemm_desc *d) {
-  if (!conv3r_bc(d)) return "invalid";
-  const R3Pick k = r3_pick(d);
-  static char names[4][5][2][40];
-  static char segnames[2][2][2][40];
-  char *n;
-  if (k.sg) {
-    // conv3r_kernel<s2,BC> (32-column segments), <s1,BC> (16-column); ",w8":
-    // 8-wave workgroups
-    n = segnames[k.sg - 1][k.bc == 128][k.nwv == 8];
-    if (!n[0]) snprintf(n, 40, "conv3r_kernel<s%d,%d%s>", k.sg, k.bc, k.nwv == 8 ? ",w8" : "");
-    return n;
-  }
+// conv3r_kernel<W,BC> (128 x 64 wave tiles), <W,BC,32> (128 x 32); row-segment
+// tiles: <s2,BC> (32-column segments), <s1,BC> (16-column); the 8-wave
+// one-per-CU variant adds ",w8"
+const char *conv3r_name(const rr_igemm_desc *d, R3Pick k) {
+#define C3_W8(s) {"conv3r_kernel<" s ">", "conv3r_kernel<" s ",w8>"}
+#define C3_W(w) {C3_W8(#w ",64"), C3_W8(#w ",64,32"), C3_W8(#w ",128"), C3_W8(#w ",128,32")}
+  static const char *const names[4][4][2] = {C3_W(8), C3_W(16), C3_W(32), C3_W(64)};
+  static const char *const segnames[2][2][2] = {{C3_W8("s1,64"), C3_W8("s1,128")}, {C3_W8("s2,64"), C3_W8("s2,128")}};
+#undef C3_W
+#undef C3_W8
+  if (k.sg) return segnames[k.sg - 1][k.bc == 128][k.nwv == 8];
   const int wi = d->w == 8 ? 0 : d->w == 16 ? 1 : d->w == 32 ? 2 : 3;
-  const int bi = k.bc == 64 ? (k.nw == 64 ? 0 : 4) : (k.nw == 64 ? 1 : 2);
-  const int vi = k.nwv == 8;
-  n = names[wi][bi][vi];
-  if (!n[0]) {
-    // conv3r_kernel<W,BC> (128 x 64 wave tiles), <W,BC,32> (128 x 32); the
-    // 8-wave one-per-CU variant adds ",w8"
-    snprintf(n, 40, "conv3r_kernel<%d,%d%s%s>", d->w, k.bc, k.nw == 32 ? ",32" : "", vi ? ",w8" : "");
-  }
-  return n;
+  return names[wi][(k.bc == 128) * 2 + (k.nw == 32)][k.nwv == 8];
 }
 
 #ifdef RR_CONV3R_STAMPS

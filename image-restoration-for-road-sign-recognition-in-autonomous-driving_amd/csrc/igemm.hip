@@ -31,10 +31,8 @@
 // (mask > 0) relu-backward mask, split of the columns over two destinations
 // (the grads of a torch.cat's two halves), convT 2x2 pixel scatter.
 #include "common.h"
-#include "stream3.h"
-#include "stream1.h"
 #include "igemm_epi.h"
-#include "conv3r.h"
+#include "route.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -1011,9 +1009,9 @@ Tile pick_tile(const rr_igemm_desc *d) {
 }
 
 // halo path eligibility (bf16 3x3, whole-row 256-pixel tiles); returns BC or 0
-int halo_bc(const rr_igemm_desc *d) {
+int halo_bc(const rr_igemm_desc *d, const RrPath &p) {
   // RR_PATH igemm_halo=0: the per-tap tiled kernel instead (tests)
-  if (!rr_path("igemm_halo", 1) || d->dtype != RR_BF16 || d->mode != RR_CONV3X3) return 0;
+  if (!p.igemm_halo || d->dtype != RR_BF16 || d->mode != RR_CONV3X3) return 0;
   // NCHW fp32 output only through the narrow 16-column tile (image grads)
   if (d->out_nchw && (d->c_out > 16 || d->want_stats || d->c_in2)) return 0;
   const int W = d->w;
@@ -1053,31 +1051,107 @@ int launch_halo(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
 }
 
 template <typename T>
-int dispatch(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {
-    const int hb = halo_bc(d);
-    if (hb == 128) return launch_halo<128, 256>(d, a, st);
-    if (hb == 64) return launch_halo<64, 256>(d, a, st);
-    if (hb == 16) return launch_halo<16, 256>(d, a, st);
-  }
-  const Tile t = pick_tile(d);
-  if (t.bc == 128) return launch_mode<T, 128, 128, 2>(d, a, st);
-  if (t.bp == 256) return launch_mode<T, 64, 256, 1>(d, a, st);
+int launch_tiled(const rr_igemm_desc *d, IgemmArgs &a, const ConvRoute &r, hipStream_t st) {
+  if (r.tile_bc == 128) return launch_mode<T, 128, 128, 2>(d, a, st);
+  if (r.tile_bp == 256) return launch_mode<T, 64, 256, 1>(d, a, st);
   return launch_mode<T, 64, 128, 2>(d, a, st);
+}
+
+// the LDS-halo or the tiled kernel of route r
+int dispatch(const rr_igemm_desc *d, IgemmArgs &a, const ConvRoute &r, hipStream_t st) {
+  if (r.family == CF_HALO) {
+    if (r.halo_bc == 128) return launch_halo<128, 256>(d, a, st);
+    if (r.halo_bc == 64) return launch_halo<64, 256>(d, a, st);
+    return launch_halo<16, 256>(d, a, st);
+  }
+  return d->dtype == RR_BF16 ? launch_tiled<bf16_t>(d, a, r, st) : launch_tiled<float>(d, a, r, st);
+}
+
+const char *halo_name(int hb, int w) {
+#define HN(bc) {"igemm3_halo_kernel<" #bc ",8>", "igemm3_halo_kernel<" #bc ",16>", "igemm3_halo_kernel<" #bc ",32>", "igemm3_halo_kernel<" #bc ",64>"}
+  static const char *const names[3][4] = {HN(16), HN(64), HN(128)};
+#undef HN
+  return names[hb == 16 ? 0 : hb == 64 ? 1 : 2][w == 8 ? 0 : w == 16 ? 1 : w == 32 ? 2 : 3];
+}
+
+const char *tiled_name(const rr_igemm_desc *d, Tile t) {
+#define TN(ty, tl) {"igemm_kernel<" ty "," tl ",m0>", "igemm_kernel<" ty "," tl ",m1>", "igemm_kernel<" ty "," tl ",m2>", "igemm_kernel<" ty "," tl ",m3>"}
+  static const char *const tn[2][3][4] = {{TN("f32", "128,128"), TN("f32", "64,256"), TN("f32", "64,128")},
+                                          {TN("bf16", "128,128"), TN("bf16", "64,256"), TN("bf16", "64,128")}};
+#undef TN
+  const int ti = t.bc == 128 ? 0 : (t.bp == 256 ? 1 : 2);
+  const int mi = d->mode >= 0 && d->mode <= 3 ? d->mode : 0;
+  return tn[d->dtype == RR_BF16][ti][mi];
+}
+
+// the descriptors rr_igemm_pool, rr_igemm_dgrad_sc and rr_igemm_pre are for
+// (anything else is RR_EINVAL there)
+bool pool_desc_ok(const rr_igemm_desc *d) {
+  return d->mode == RR_CONV3X3 && d->act == RR_ACT_RELU && !d->out_split && !d->accumulate &&
+         !d->has_mask && !d->want_stats && !d->out_nchw && d->h >= 2 && d->w >= 2;
+}
+bool sc_desc_ok(const rr_igemm_desc *d) {
+  return d->mode == RR_CONV3X3 && !d->act && !d->has_bias && !d->want_stats && !d->has_mask &&
+         !d->out_split && !d->accumulate && !d->out_nchw && !d->c_in2;
+}
+bool pre_desc_ok(const rr_igemm_desc *d) {
+  return d->mode == RR_CONV3X3 && d->act == RR_ACT_NONE && d->has_bias && d->want_stats &&
+         !d->accumulate && !d->has_mask && !d->c_in2;
 }
 
 }  // namespace
 
+// The one routing decision: stream3 -> stream1 -> conv3r -> LDS-halo -> tiled,
+// each family asked once.  The plain and BN-backward kinds always end on a
+// kernel; the eval epilogues and the pool have stream3 and conv3r instances
+// only, the 1x1 second source and the input transform stream3 ones only
+// (CF_NONE, "unsupported", otherwise).
+ConvRoute conv_route(const rr_igemm_desc *d, const RrPath &p, int kind) {
+  ConvRoute r{};
+  r.family = CF_NONE;
+  r.name = "unsupported";
+  // (the pool epilogue needs a 2x2 window)
+  if (kind == CK_EX && (d->act & RR_ACT_POOL) && (d->h < 2 || d->w < 2)) return r;
+  if ((kind == CK_POOL || kind == CK_POOL_IDX) && !pool_desc_ok(d)) return r;
+  if (kind == CK_DGRAD_SC && !sc_desc_ok(d)) return r;
+  if (kind == CK_PRE && !pre_desc_ok(d)) return r;
+  r.s3 = stream3_pick(d, p, kind);
+  if (r.s3.flags >= 0) {
+    r.family = CF_STREAM3;
+    r.rows = stream3_rows();
+    r.name = stream3_name(d, r.s3, kind);
+    return r;
+  }
+  if (kind == CK_DGRAD_SC || kind == CK_PRE) return r;
+  if (kind == CK_PLAIN && (r.rows = stream1_plan(d, p, &r.s1)) != 0) {
+    r.family = CF_STREAM1;
+    r.name = stream1_name(r.s1);
+    return r;
+  }
+  if (conv3r_bc(d, p, &r.r3)) {
+    r.family = CF_CONV3R;
+    r.rows = conv3r_rows(d, r.r3);
+    r.name = conv3r_name(d, r.r3);
+    return r;
+  }
+  if (kind != CK_PLAIN && kind != CK_BNBWD) return r;
+  const long long P = (long long)d->n * d->h * d->w;
+  r.halo_bc = halo_bc(d, p);
+  const Tile t = pick_tile(d);
+  r.tile_bc = t.bc; r.tile_bp = t.bp;
+  r.family = r.halo_bc ? CF_HALO : CF_TILED;
+  const int bp = r.halo_bc ? 256 : t.bp;
+  r.rows = (int)((P + bp - 1) / bp);
+  r.name = r.halo_bc ? halo_name(r.halo_bc, d->w) : tiled_name(d, t);
+  return r;
+}
+
+// rows of the BN statistics partial slab rr_igemm writes for *d; the
+// BN-backward partial slabs (rr_igemm_bnbwd) are sized with it too, from the
+// plain call's route of the same descriptor
 extern "C" int rr_igemm_stat_blocks(const rr_igemm_desc *d) {
   if (!d) return RR_EINVAL;
-  if (const int sb = stream3_blocks(d, 0)) return sb;
-  S1Plan pl;
-  if (const int g = stream1_plan(d, &pl)) return g;
-  if (const int r = conv3r_stat_blocks(d)) return r;
-  const long long P = (long long)d->n * d->h * d->w;
-  const int hb = halo_bc(d);
-  const int bp = hb ? 256 : pick_tile(d).bp;
-  return (int)((P + bp - 1) / bp);
+  return conv_route(d, rr_path_read(), CK_PLAIN).rows;
 }
 
 static int fill_args(const rr_igemm_desc *d, const void *x1, const void *x2, const void *w,
@@ -1121,74 +1195,47 @@ static int fill_args(const rr_igemm_desc *d, const void *x1, const void *x2, con
   return RR_OK;
 }
 
-// the kernel rr_igemm would launch for *d (same decisions as rr_igemm /
-// dispatch; bench.py names its roofline kernel and the tests assert the
-// benched schedule with it).  Static strings, never NULL.
+// the kernel rr_igemm / rr_igemm_ex (act beyond ReLU) / rr_igemm_bnbwd
+// launches for *d: the route's name (bench.py names its roofline kernel and
+// the tests assert the benched schedule with it).  Static strings, never NULL.
 extern "C" const char *rr_igemm_kernel_name(const rr_igemm_desc *d, int bnbwd) {
   if (!d) return "invalid";
-  if (d->act > RR_ACT_RELU) {
-    // (the pool epilogue needs a 2x2 window: rr_igemm_ex refuses such maps)
-    if ((d->act & RR_ACT_POOL) && (d->h < 2 || d->w < 2)) return "unsupported";
-    if (!bnbwd && stream3_ex_ok(d)) return stream3_name(d, "");
-    return !bnbwd && conv3r_bc(d) ? conv3r_name(d) : "unsupported";
-  }
-  if (stream3_blocks(d, bnbwd)) return stream3_name(d, "");
-  S1Plan pl;
-  if (!bnbwd && stream1_plan(d, &pl)) return stream1_name(pl);
-  if (conv3r_bc(d)) return conv3r_name(d);
-  if (d->dtype == RR_BF16) {
-    const int hb = halo_bc(d);
-    if (hb) {
-      static const char *names[3][4] = {
-          {"igemm3_halo_kernel<16,8>", "igemm3_halo_kernel<16,16>", "igemm3_halo_kernel<16,32>", "igemm3_halo_kernel<16,64>"},
-          {"igemm3_halo_kernel<64,8>", "igemm3_halo_kernel<64,16>", "igemm3_halo_kernel<64,32>", "igemm3_halo_kernel<64,64>"},
-          {"igemm3_halo_kernel<128,8>", "igemm3_halo_kernel<128,16>", "igemm3_halo_kernel<128,32>", "igemm3_halo_kernel<128,64>"}};
-      const int wi = d->w == 8 ? 0 : d->w == 16 ? 1 : d->w == 32 ? 2 : 3;
-      const int bi = hb == 16 ? 0 : hb == 64 ? 1 : 2;
-      return names[bi][wi];
-    }
-  }
-  const Tile t = pick_tile(d);
-  const bool b = d->dtype == RR_BF16;
-  static const char *tn[2][3][4] = {
-      {{"igemm_kernel<f32,128,128,m0>", "igemm_kernel<f32,128,128,m1>", "igemm_kernel<f32,128,128,m2>", "igemm_kernel<f32,128,128,m3>"},
-       {"igemm_kernel<f32,64,256,m0>", "igemm_kernel<f32,64,256,m1>", "igemm_kernel<f32,64,256,m2>", "igemm_kernel<f32,64,256,m3>"},
-       {"igemm_kernel<f32,64,128,m0>", "igemm_kernel<f32,64,128,m1>", "igemm_kernel<f32,64,128,m2>", "igemm_kernel<f32,64,128,m3>"}},
-      {{"igemm_kernel<bf16,128,128,m0>", "igemm_kernel<bf16,128,128,m1>", "igemm_kernel<bf16,128,128,m2>", "igemm_kernel<bf16,128,128,m3>"},
-       {"igemm_kernel<bf16,64,256,m0>", "igemm_kernel<bf16,64,256,m1>", "igemm_kernel<bf16,64,256,m2>", "igemm_kernel<bf16,64,256,m3>"},
-       {"igemm_kernel<bf16,64,128,m0>", "igemm_kernel<bf16,64,128,m1>", "igemm_kernel<bf16,64,128,m2>", "igemm_kernel<bf16,64,128,m3>"}}};
-  const int ti = t.bc == 128 ? 0 : (t.bp == 256 ? 1 : 2);
-  const int mi = d->mode >= 0 && d->mode <= 3 ? d->mode : 0;
-  return tn[b][ti][mi];
+  const bool ex = d->act > RR_ACT_RELU;
+  if (ex && bnbwd) return "unsupported";
+  return conv_route(d, rr_path_read(), ex ? CK_EX : bnbwd ? CK_BNBWD : CK_PLAIN).name;
 }
 
-extern "C" int rr_igemm(const rr_igemm_desc *d, const void *x1, const void *x2,
-                        const void *w, const float *bias, void *y1, void *y2,
-                        const void *mask, float *stats_partial, rr_stream stream) {
+static int igemm_plain(const rr_igemm_desc *d, const RrPath &p, const void *x1, const void *x2,
+                       const void *w, const float *bias, void *y1, void *y2, const void *mask,
+                       float *stats_partial, hipStream_t st) {
   if (d && (d->act < 0 || d->act > RR_ACT_RELU)) return RR_EINVAL;   // (PReLU / residual: rr_igemm_ex)
   IgemmArgs a;
   const int rc = fill_args(d, x1, x2, w, bias, y1, y2, mask, stats_partial, a);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (stream3_blocks(d, 0)) {
+  const ConvRoute r = conv_route(d, p, CK_PLAIN);
+  if (r.family == CF_STREAM3) {
     S3Args s{};
     s.x = a.x1; s.x2 = a.x2; s.wt = a.wt; s.bias = a.bias; s.y = a.y1;
     s.mask = d->has_mask ? a.mask : nullptr;
     s.stats = a.stats;
     s.n = d->n; s.h = d->h; s.w = d->w; s.act = d->act; s.accumulate = d->accumulate;
-    return stream3_launch(d, s, 0, st);
+    return stream3_launch(d, s, r.s3, st);
   }
-  S1Plan pl;
-  if (stream1_plan(d, &pl)) {
+  if (r.family == CF_STREAM1) {
     S1Args s{};
     s.x1 = a.x1; s.x2 = a.x2; s.wt = a.wt; s.bias = a.bias; s.y1 = a.y1; s.y2 = a.y2;
     s.mask = d->has_mask ? a.mask : nullptr;
     s.stats = a.stats;
-    return stream1_launch(d, pl, s, st);
+    return stream1_launch(d, r.s1, s, st);
   }
-  if (conv3r_bc(d)) return conv3r_launch(d, a, st);
-  if (d->dtype == RR_BF16) return dispatch<bf16_t>(d, a, st);
-  return dispatch<float>(d, a, st);
+  if (r.family == CF_CONV3R) return conv3r_launch(d, a, r.r3, st);
+  return dispatch(d, a, r, st);
+}
+
+extern "C" int rr_igemm(const rr_igemm_desc *d, const void *x1, const void *x2,
+                        const void *w, const float *bias, void *y1, void *y2,
+                        const void *mask, float *stats_partial, rr_stream stream) {
+  return igemm_plain(d, rr_path_read(), x1, x2, w, bias, y1, y2, mask, stats_partial, (hipStream_t)stream);
 }
 
 extern "C" int rr_igemm_ex(const rr_igemm_desc *d, const void *x1, const void *x2, const void *w,
@@ -1201,7 +1248,12 @@ extern "C" int rr_igemm_ex(const rr_igemm_desc *d, const void *x1, const void *x
   if ((d->act & RR_ACT_POOL) && (!y_pool || d->out_split || d->h < 2 || d->w < 2)) return RR_EINVAL;
   if ((d->act & RR_ACT_NOFULL) && (!(d->act & RR_ACT_POOL) || d->accumulate || d->want_stats))
     return RR_EINVAL;
-  if (d->act > RR_ACT_RELU && stream3_ex_ok(d)) {
+  const RrPath p = rr_path_read();
+  hipStream_t st = (hipStream_t)stream;
+  if (d->act <= RR_ACT_RELU)
+    return igemm_plain(d, p, x1, x2, w, bias, y1, nullptr, mask, stats_partial, st);
+  const ConvRoute r = conv_route(d, p, CK_EX);
+  if (r.family == CF_STREAM3) {
     // the 64 -> 64 maps the streaming kernel takes (whole rows, or column
     // strips of the reference's 224 maps)
     if (!x1 || !w || !bias || (!y1 && !(d->act & RR_ACT_NOFULL))) return RR_EINVAL;
@@ -1210,22 +1262,18 @@ extern "C" int rr_igemm_ex(const rr_igemm_desc *d, const void *x1, const void *x
     s.y = (d->act & RR_ACT_NOFULL) ? nullptr : (char *)y1;
     s.n = d->n; s.h = d->h; s.w = d->w; s.act = d->act;
     s.alpha = alpha; s.res = (const char *)res; s.ypool = (char *)y_pool;
-    return stream3_launch_ex(d, s, (hipStream_t)stream);
+    return stream3_launch(d, s, r.s3, st);
   }
-  if (d->act > RR_ACT_RELU && !conv3r_bc(d)) return RR_EUNSUPPORTED;
+  if (r.family != CF_CONV3R) return RR_EUNSUPPORTED;
   // (y1 unused with RR_ACT_NOFULL: fill_args wants a pointer)
   void *y1a = (d->act & RR_ACT_NOFULL) ? y_pool : y1;
   IgemmArgs a;
   const int rc = fill_args(d, x1, x2, w, bias, y1a, nullptr, mask, stats_partial, a);
   if (rc) return rc;
-  if (d->act <= RR_ACT_RELU) {
-    rr_igemm_desc d2 = *d;
-    return rr_igemm(&d2, x1, x2, w, bias, y1, nullptr, mask, stats_partial, stream);
-  }
   a.alpha = alpha;
   a.res = (const char *)res;
   a.ypool = (char *)y_pool;
-  return conv3r_launch(d, a, (hipStream_t)stream);
+  return conv3r_launch(d, a, r.r3, st);
 }
 
 // conv2's bias + BN-statistics forward with BN1 + PReLU of its input folded
@@ -1233,10 +1281,7 @@ extern "C" int rr_igemm_ex(const rr_igemm_desc *d, const void *x1, const void *x
 // rr_affine_act would store): the row-streaming kernel's 64 -> 64 whole-row
 // maps only (rr_igemm_pre_ok)
 extern "C" int rr_igemm_pre_ok(const rr_igemm_desc *d) {
-  return d && d->mode == RR_CONV3X3 && d->act == RR_ACT_NONE && d->has_bias && d->want_stats &&
-                 !d->accumulate && !d->has_mask && !d->c_in2 && stream3_blocks(d, 0) && !stream3_strips(d)
-             ? 1
-             : 0;
+  return d && conv_route(d, rr_path_read(), CK_PRE).family == CF_STREAM3 ? 1 : 0;
 }
 
 extern "C" int rr_igemm_pre(const rr_igemm_desc *d, const void *x1, const void *w, const float *bias,
@@ -1244,92 +1289,84 @@ extern "C" int rr_igemm_pre(const rr_igemm_desc *d, const void *x1, const void *
                             void *y1, float *stats_partial, rr_stream stream) {
   if (!d || !x1 || !w || !bias || !pre_scale || !pre_shift || !pre_alpha || !y1 || !stats_partial)
     return RR_EINVAL;
-  if (!rr_igemm_pre_ok(d)) return RR_EUNSUPPORTED;
+  const ConvRoute r = conv_route(d, rr_path_read(), CK_PRE);
+  if (r.family != CF_STREAM3) return RR_EUNSUPPORTED;
   S3Args s{};
   s.x = (const char *)x1; s.wt = (const char *)w; s.bias = bias; s.y = (char *)y1;
   s.stats = stats_partial;
   s.n = d->n; s.h = d->h; s.w = d->w; s.act = d->act;
   s.pre_s = pre_scale; s.pre_b = pre_shift; s.pre_alpha = pre_alpha;
-  return stream3_launch_pre(d, s, (hipStream_t)stream);
+  return stream3_launch(d, s, r.s3, (hipStream_t)stream);
 }
 
-// conv (+ bias) + ReLU + MaxPool2d(2, 2) with the window index, the full-size
-// output never written (the perceptual VGG slice's conv1_2 / conv2_2 + pool,
-// 14:189-196, and every no-backward pool of it): the row-streaming kernel
-// where it takes the layer, else the tap-reuse conv's register epilogue
+// conv (+ bias) + ReLU + MaxPool2d(2, 2), the full-size output never written
+// (the perceptual VGG slice's conv1_2 / conv2_2 + pool, 14:189-196, and every
+// no-backward pool of it), with the window index when pool_idx is given: the
+// row-streaming kernel where it takes the layer -- with the index on whole-row
+// maps, without it on biased layers -- else the tap-reuse conv's register
+// epilogue
 extern "C" int rr_igemm_pool(const rr_igemm_desc *d, const void *x1, const void *x2, const void *w,
                              const float *bias, void *y_pool, uint8_t *pool_idx, rr_stream stream) {
-  if (!d || !y_pool || d->mode != RR_CONV3X3 || d->act != RR_ACT_RELU || d->out_split ||
-      d->accumulate || d->has_mask || d->want_stats || d->out_nchw || d->h < 2 || d->w < 2)
-    return RR_EINVAL;
+  if (!d || !y_pool || !pool_desc_ok(d)) return RR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (stream3_blocks(d, 0) && !d->c_in2 && (pool_idx ? !stream3_strips(d) : d->has_bias)) {
+  const ConvRoute r = conv_route(d, rr_path_read(), pool_idx ? CK_POOL_IDX : CK_POOL);
+  if (r.family == CF_STREAM3) {
+    if (!x1 || !w || (d->has_bias && !bias)) return RR_EINVAL;
     S3Args s{};
     s.x = (const char *)x1; s.wt = (const char *)w; s.bias = d->has_bias ? bias : nullptr;
     s.n = d->n; s.h = d->h; s.w = d->w; s.act = d->act;
     s.ypool = (char *)y_pool; s.pidx = pool_idx;
-    if (!x1 || !w || (d->has_bias && !bias)) return RR_EINVAL;
-    return stream3_launch_pool(d, s, st);
+    return stream3_launch(d, s, r.s3, st);
   }
+  if (r.family != CF_CONV3R) return RR_EUNSUPPORTED;
   rr_igemm_desc d2 = *d;
   d2.act = RR_ACT_RELU | RR_ACT_POOL | RR_ACT_NOFULL;
-  if (!conv3r_bc(&d2)) return RR_EUNSUPPORTED;
   IgemmArgs a;
   const int rc = fill_args(&d2, x1, x2, w, bias, y_pool, nullptr, nullptr, nullptr, a);
   if (rc) return rc;
   a.ypool = (char *)y_pool;
   a.pidx = pool_idx;
-  return conv3r_launch(&d2, a, st);
+  return conv3r_launch(&d2, a, r.r3, st);
 }
 
-// the kernel rr_igemm_pool launches for *d ("unsupported" when neither takes it)
-extern "C" const char *rr_igemm_pool_kernel_name(const rr_igemm_desc *d) {
-  if (!d || d->mode != RR_CONV3X3 || d->act != RR_ACT_RELU || d->out_split || d->accumulate ||
-      d->has_mask || d->want_stats || d->out_nchw || d->h < 2 || d->w < 2)
-    return "unsupported";
-  if (stream3_blocks(d, 0) && !d->c_in2) return stream3_name(d, "pool");
-  rr_igemm_desc d2 = *d;
-  d2.act = RR_ACT_RELU | RR_ACT_POOL | RR_ACT_NOFULL;
-  return conv3r_bc(&d2) ? conv3r_name(&d2) : "unsupported";
+// the kernel rr_igemm_pool launches for *d with (with_index != 0) or without
+// the window index ("unsupported" when neither family takes it)
+extern "C" const char *rr_igemm_pool_kernel_name(const rr_igemm_desc *d, int with_index) {
+  if (!d) return "unsupported";
+  return conv_route(d, rr_path_read(), with_index ? CK_POOL_IDX : CK_POOL).name;
 }
 
 // the 3x3 dgrad plus the 1x1 dgrad of a second gradient into one output, one
 // pass: a ResidualBlock's input grad is conv_block[0]'s dgrad + shortcut[0]'s
 // dgrad (14:99-115) -- dec1 (64 + 64 -> 64): per concat half, instead of a
 // 3x3 dgrad and a 1x1 accumulate pass over both halves
-static bool dgrad_sc_ok(const rr_igemm_desc *d, int c_sc) {
-  return d && d->mode == RR_CONV3X3 && !d->act && !d->has_bias && !d->want_stats && !d->has_mask &&
-         !d->out_split && !d->accumulate && !d->out_nchw && !d->c_in2 && c_sc == 64 &&
-         stream3_blocks(d, 0) && !stream3_strips(d);
-}
-
 extern "C" int rr_igemm_dgrad_sc(const rr_igemm_desc *d, const void *dy, const void *w,
                                  const void *dy_sc, const void *w_sc, int c_sc, void *y,
                                  rr_stream stream) {
   if (!d || !dy || !w || !dy_sc || !w_sc || !y || c_sc <= 0) return RR_EINVAL;
-  if (d->mode != RR_CONV3X3 || d->act || d->has_bias || d->want_stats || d->has_mask ||
-      d->out_split || d->accumulate || d->out_nchw || d->c_in2)
-    return RR_EINVAL;
-  if (!dgrad_sc_ok(d, c_sc)) return RR_EUNSUPPORTED;
+  if (!sc_desc_ok(d)) return RR_EINVAL;
+  const ConvRoute r = conv_route(d, rr_path_read(), CK_DGRAD_SC);
+  if (c_sc != 64 || r.family != CF_STREAM3) return RR_EUNSUPPORTED;
   S3Args s{};
   s.x = (const char *)dy; s.wt = (const char *)w; s.y = (char *)y;
   s.n = d->n; s.h = d->h; s.w = d->w;
   s.xsc = (const char *)dy_sc; s.wsc = (const char *)w_sc;
-  return stream3_launch_sc(d, s, (hipStream_t)stream);
+  return stream3_launch(d, s, r.s3, (hipStream_t)stream);
 }
 
 extern "C" const char *rr_igemm_dgrad_sc_kernel_name(const rr_igemm_desc *d, int c_sc) {
-  if (!dgrad_sc_ok(d, c_sc)) return "unsupported";
-  return stream3_name(d, "sc");
+  if (!d || c_sc != 64) return "unsupported";
+  return conv_route(d, rr_path_read(), CK_DGRAD_SC).name;
 }
 
-static int bnbwd_rows(const rr_igemm_desc *d) { return rr_igemm_stat_blocks(d); }
+static size_t bnbwd_bytes(const rr_igemm_desc *d, int rows) {
+  return ((size_t)rows * d->c_out * 3 + (size_t)rows * (d->c_out / 64)) * sizeof(float);
+}
 
 extern "C" size_t rr_igemm_bnbwd_workspace(const rr_igemm_desc *d) {
   if (!d || d->c_out <= 0) return 0;
-  const int rows = bnbwd_rows(d);
-  if (rows <= 0) return 0;
-  return ((size_t)rows * d->c_out * 3 + (size_t)rows * (d->c_out / 64)) * sizeof(float);
+  const int rows = rr_igemm_stat_blocks(d);
+  return rows <= 0 ? 0 : bnbwd_bytes(d, rows);
 }
 
 extern "C" int rr_igemm_bnbwd(const rr_igemm_desc *d, const void *dy, const void *w,
@@ -1347,20 +1384,23 @@ extern "C" int rr_igemm_bnbwd(const rr_igemm_desc *d, const void *dy, const void
   IgemmArgs a;
   const int rc = fill_args(d, dy, nullptr, w, nullptr, gm_out, nullptr, nullptr, nullptr, a);
   if (rc) return rc;
+  const RrPath p = rr_path_read();
+  const ConvRoute r = conv_route(d, p, CK_BNBWD);
   a.bt = (const char *)t;
   a.bmean = mean; a.binv = invstd; a.baff_s = aff_s; a.baff_b = aff_b; a.balpha = alpha;
   a.bpart = partial;
-  a.bapart = partial + (size_t)bnbwd_rows(d) * d->c_out * 3;
+  // (the alpha partials follow the rows the caller sized the slabs with:
+  // rr_igemm_stat_blocks, the plain call's route)
+  a.bapart = partial + (size_t)conv_route(d, p, CK_PLAIN).rows * d->c_out * 3;
   hipStream_t st = (hipStream_t)stream;
-  if (stream3_blocks(d, 1)) {
+  if (r.family == CF_STREAM3) {
     S3Args s{};
     s.x = a.x1; s.wt = a.wt; s.y = a.y1;
     s.n = d->n; s.h = d->h;
     s.bt = a.bt; s.bmean = mean; s.binv = invstd; s.baff_s = aff_s; s.baff_b = aff_b;
     s.balpha = alpha; s.bpart = a.bpart; s.bapart = a.bapart;
-    return stream3_launch(d, s, 1, st);
+    return stream3_launch(d, s, r.s3, st);
   }
-  if (conv3r_bc(d)) return conv3r_launch(d, a, st);
-  if (d->dtype == RR_BF16) return dispatch<bf16_t>(d, a, st);
-  return dispatch<float>(d, a, st);
+  if (r.family == CF_CONV3R) return conv3r_launch(d, a, r.r3, st);
+  return dispatch(d, a, r, st);
 }

@@ -698,10 +698,10 @@ __global__ __launch_bounds__(256) void distort_blur_tiled_kernel(DistCfg a) {
   }
 }
 
-static void launch_blur(const DistCfg &a, long long tp, hipStream_t st) {
+static void launch_blur(const DistCfg &a, long long tp, const RrPath &p, hipStream_t st) {
   // the LDS-tiled form where whole 256-pixel tiles fit (RR_PATH
   // blur_tiled=0: the per-pixel kernel, tests)
-  if (((long long)a.h * a.w) % 256 == 0 && a.c <= 4 && rr_path("blur_tiled", 1))
+  if (((long long)a.h * a.w) % 256 == 0 && a.c <= 4 && p.blur_tiled)
     hipLaunchKernelGGL(distort_blur_tiled_kernel, dim3(rr_grid_cap((tp + 255) / 256, 8192)), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(distort_blur_kernel, dim3(rr_grid_cap((tp + 255) / 256, 8192)), dim3(256), 0, st, a);
@@ -804,7 +804,7 @@ extern "C" int rr_distort_u8(int n, int h, int w, int c, int mode, const uint8_t
   const long long te = (long long)n * h * w * c, tp = (long long)n * h * w;
   hipLaunchKernelGGL(distort_pre_kernel, dim3(rr_grid_cap((te + 255) / 256, 8192)), dim3(256), 0, st, a);
   RR_CHECK_LAUNCH();
-  launch_blur(a, tp, st);
+  launch_blur(a, tp, rr_path_read(), st);
   RR_CHECK_LAUNCH();
   return RR_OK;
 }
@@ -898,7 +898,7 @@ extern "C" int rr_distort_random_u8(int n, int h, int w, int c, const uint8_t *i
   const long long te = (long long)n * h * w * c, tp = (long long)n * h * w;
   hipLaunchKernelGGL(distort_pre_kernel, dim3(rr_grid_cap((te + 255) / 256, 8192)), dim3(256), 0, st, a);
   RR_CHECK_LAUNCH();
-  launch_blur(a, tp, st);
+  launch_blur(a, tp, rr_path_read(), st);
   RR_CHECK_LAUNCH();
   return RR_OK;
 }

@@ -25,7 +25,7 @@
 // The model-boundary final conv (c_out <= 16, fp32 NCHW output) stores from
 // the accumulator layout: 16 lanes = 16 consecutive pixels of one plane.
 #include "common.h"
-#include "stream1.h"
+#include "route.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -353,16 +353,15 @@ int ilog2(int v) {
 
 }  // namespace
 
-int stream1_plan(const rr_igemm_desc *d, S1Plan *pl) {
+int stream1_plan(const rr_igemm_desc *d, const RrPath &p, S1Plan *pl) {
   // RR_PATH stream1=0: the tiled igemm instead; stream1_minp=N: stream from
   // N pixels (the tests' small shapes; default 131072, measured, r5ze)
-  if (!rr_path("stream1", 1)) return 0;
+  if (!p.stream1) return 0;
   if (!d || d->dtype != RR_BF16) return 0;
   const int mode = d->mode;
   if (mode != RR_CONV1X1 && mode != RR_CONVT_UP && mode != RR_CONVT_DOWN) return 0;
   const long long P = (long long)d->n * d->h * d->w;
-  const long long minp = rr_path("stream1_minp", 131072);
-  if (P < minp || P % 16 || P * 16 > 0x7fffffffLL) return 0;
+  if (P < p.stream1_minp || P % 16 || P * 16 > 0x7fffffffLL) return 0;
   const int cin = d->c_in1 + d->c_in2;
   const int taps = mode == RR_CONVT_DOWN ? 4 : 1;
   if (d->c_in1 % 32 || d->c_in2 % 32) return 0;
@@ -431,12 +430,9 @@ int stream1_launch(const rr_igemm_desc *d, const S1Plan &pl, S1Args a, hipStream
 }
 
 const char *stream1_name(const S1Plan &pl) {
-  static const char *names[9][17] = {};
-  static char buf[9][17][32];
-  if (pl.mc < 1 || pl.mc > 8 || pl.kb < 1 || pl.kb > 16) return "stream1_kernel<?>";
-  if (!names[pl.mc][pl.kb]) {
-    snprintf(buf[pl.mc][pl.kb], sizeof buf[0][0], "stream1_kernel<%d,%d>", pl.mc, pl.kb);
-    names[pl.mc][pl.kb] = buf[pl.mc][pl.kb];
-  }
-  return names[pl.mc][pl.kb];
+#define S1_NAME(MC_, KB_, st, md, nc, eo) \
+  if (pl.mc == MC_ && pl.kb == KB_) return "stream1_kernel<" #MC_ "," #KB_ ">";
+  S1_LIST(S1_NAME)
+#undef S1_NAME
+  return "stream1_kernel<?>";
 }

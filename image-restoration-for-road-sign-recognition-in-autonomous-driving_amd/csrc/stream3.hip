@@ -51,7 +51,7 @@
 // flight hipcc waits vmcnt(0) / lgkmcnt(0) for the results of ordinary
 // loads, which would drain the prefetch every step.
 #include "common.h"
-#include "stream3.h"
+#include "route.h"
 
 #include <climits>
 #include <cstdlib>
@@ -865,10 +865,9 @@ __global__ __launch_bounds__(512, 2) void stream3_kernel(S3Args a, int nsteps) {
   }
 }
 
-// epilogue flag set of a call, or -1 when the streaming kernel has no
+// epilogue flag set of a plain call, or -1 when the streaming kernel has no
 // instance for it (the tiled kernel takes the call)
-int s3_flags(const rr_igemm_desc *d, bool bnbwd) {
-  if (bnbwd) return F_BNBWD;
+int s3_flags(const rr_igemm_desc *d) {
   const int f = (d->has_bias ? F_BIAS : 0) | (d->want_stats ? F_STATS : 0) |
                 (d->act == RR_ACT_RELU ? F_RELU : 0) | (d->accumulate ? F_ACC : 0) |
                 (d->has_mask ? F_MASK : 0);
@@ -913,7 +912,7 @@ int launch_w(const S3Args &a, int f, int P, hipStream_t st) {
     case F_ACC | F_MASK: launch1<W, 2, F_ACC | F_MASK>(a, P, st); break;
     case F_BNBWD: launch1<W, 2, F_BNBWD>(a, P, st); break;
     case F_BIAS | F_STATS | F_PRE: launch1<W, 2, F_BIAS | F_STATS | F_PRE, 0>(a, P, st); break;
-    // the eval epilogues (stream3_launch_ex), 128-pixel steps
+    // the eval epilogues (rr_igemm_ex), 128-pixel steps
     case F_BIAS | F_PRELU: launch1<W, 2, F_BIAS | F_PRELU, 0>(a, P, st); break;
     case F_BIAS | F_RES | F_RELU: launch1<W, 2, F_BIAS | F_RES | F_RELU, 0>(a, P, st); break;
     case F_BIAS | F_RES | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
@@ -921,6 +920,14 @@ int launch_w(const S3Args &a, int f, int P, hipStream_t st) {
     case F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
       launch1<W, 2, F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX, 0>(a, P, st); break;
     case F_BIAS | F_RELU | F_POOL | F_PNOIDX: launch1<W, 2, F_BIAS | F_RELU | F_POOL | F_PNOIDX, 0>(a, P, st); break;
+    // the pool with its window index (rr_igemm_pool) and the 1x1 second
+    // source (rr_igemm_dgrad_sc): 128-pixel steps, no stagger -- the bias +
+    // ReLU forward's and the plain dgrad's form (256-pixel steps at W = 64
+    // were bitwise equal and within the run order's noise,
+    // profiles/r5zi_pool_bench.jsonl, r5zj_pool_bench.jsonl)
+    case F_BIAS | F_RELU | F_POOL: launch1<W, 2, F_BIAS | F_RELU | F_POOL, 0>(a, P, st); break;
+    case F_RELU | F_POOL: launch1<W, 2, F_RELU | F_POOL, 0>(a, P, st); break;
+    case F_SC: launch1<W, 2, F_SC, 0>(a, P, st); break;
     default: return RR_EUNSUPPORTED;
   }
   RR_CHECK_LAUNCH();
@@ -973,26 +980,18 @@ int s3_col(int w) {
   return 0;
 }
 
-bool s3_is_strip(const rr_igemm_desc *d) { return s3_col(d->w) != d->w; }
-
-// launch flag set f of *d: whole rows or strips
-int s3_go(const rr_igemm_desc *d, const S3Args &a, int f, int P, hipStream_t st) {
-  if (s3_is_strip(d)) return launch_strips(a, f, P, st);
-  if (d->w == 64) return launch_w<64>(a, f, P, st);
-  return launch_w<32>(a, f, P, st);
-}
-
 }  // namespace
 
-int stream3_geom_ok(const rr_igemm_desc *d) {
+// the geometry the streaming kernel walks: 0, or the column width
+static int stream3_geom_ok(const rr_igemm_desc *d, const RrPath &p) {
   // RR_PATH stream3=0: the tap-reuse / halo kernels instead (tests)
-  if (!rr_path("stream3", 1)) return 0;
+  if (!p.stream3) return 0;
   if (d->dtype != RR_BF16 || d->mode != RR_CONV3X3) return 0;
   if (d->c_in1 != 64 || d->c_out != 64 || d->out_split || d->out_nchw) return 0;
   const int cw = s3_col(d->w);
   // column strips: RR_PATH stream3_strips=0 leaves the wide maps to the
   // tap-reuse conv's row-segment tiles
-  if (!cw || (cw != d->w && !rr_path("stream3_strips", 1))) return 0;
+  if (!cw || (cw != d->w && !p.stream3_strips)) return 0;
   // eligibility independent of the step size: whole 256-pixel steps (the
   // larger one) and at least one per workgroup
   if (d->h % (256 / cw)) return 0;
@@ -1000,45 +999,13 @@ int stream3_geom_ok(const rr_igemm_desc *d) {
   // (every element offset is 64-bit: the cfg5 chunks of 1024 224x224 images
   // are 6.6 GB per tensor)
   if (P < 256LL * S3_WG || P > INT_MAX / 2) return 0;
-  return S3_WG;
-}
-
-int stream3_blocks(const rr_igemm_desc *d, int bnbwd) {
-  if (!stream3_geom_ok(d)) return 0;
-  // (a concat input, dec1's 64 + 64 -> 64, goes to the tap-reuse conv in
-  // one pass with the whole K = 1152 sum in fp32: the same graph-step time
-  // as two streaming passes, profiles/r4j_abstep_concat_splitdgrad.txt,
-  // without a bf16 rounding of the half sum)
-  const int f = s3_flags(d, bnbwd != 0);
-  if (d->c_in2 != 0 || f < 0 || (s3_is_strip(d) && !s3_strip_flags(f))) return 0;
-  return S3_WG;
-}
-
-int stream3_strips(const rr_igemm_desc *d) { return stream3_geom_ok(d) && s3_is_strip(d); }
-
-const char *stream3_name(const rr_igemm_desc *d, const char *suffix) {
-  static const char *names[4][5] = {
-      {"stream3_kernel<64>", "stream3_kernel<64,pool>", "stream3_kernel<64,sc>", "stream3_kernel<64,ex>", "stream3_kernel<64,bnbwd>"},
-      {"stream3_kernel<32>", "stream3_kernel<32,pool>", "stream3_kernel<32,sc>", "stream3_kernel<32,ex>", "stream3_kernel<32,bnbwd>"},
-      {"stream3_kernel<s64>", "stream3_kernel<s64,pool>", "stream3_kernel<s64,sc>", "stream3_kernel<s64,ex>", "stream3_kernel<s64,bnbwd>"},
-      {"stream3_kernel<s32>", "stream3_kernel<s32,pool>", "stream3_kernel<s32,sc>", "stream3_kernel<s32,ex>", "stream3_kernel<s32,bnbwd>"}};
-  const int cw = s3_col(d->w);
-  const int r = (cw == d->w ? 0 : 2) + (cw == 64 ? 0 : 1);   // (strips: 32 wide)
-  int c = 0;
-  if (suffix && suffix[0]) {
-    switch (suffix[0]) {
-      case 'p': c = 1; break;
-      case 's': c = 2; break;
-      case 'e': c = 3; break;
-      default: c = 4; break;
-    }
-  }
-  return names[r][c];
+  return cw;
 }
 
 // the eval flag set of an rr_igemm_ex call, or -1
 static int s3_ex_flags(const rr_igemm_desc *d) {
   if (!d->has_bias || d->want_stats || d->accumulate || d->has_mask) return -1;
+  if ((d->act & RR_ACT_POOL) && (d->h % 2 || d->w % 2)) return -1;
   const int act = d->act;
   const bool prelu = (act & 3) == RR_ACT_PRELU, relu = (act & 3) == RR_ACT_RELU;
   const bool res = (act & RR_ACT_RES) != 0, pool = (act & RR_ACT_POOL) != 0, full = !(act & RR_ACT_NOFULL);
@@ -1050,21 +1017,51 @@ static int s3_ex_flags(const rr_igemm_desc *d) {
   return -1;
 }
 
-int stream3_ex_ok(const rr_igemm_desc *d) {
-  if (!stream3_geom_ok(d) || d->c_in2 != 0) return 0;
-  if ((d->act & RR_ACT_POOL) && (d->h % 2 || d->w % 2)) return 0;
-  return s3_ex_flags(d) >= 0 ? S3_WG : 0;
+// The flag set of *d as call kind `kind` (conv_route has checked the kind's
+// own descriptor rules).  The plain flag set, or the kind's own for the BN
+// backward and the eval epilogues, must have an instance -- on a strip map a
+// strip instance -- before the pool / 1x1-source / input-transform kinds add
+// their flag: those have whole-row instances only, except the index-free pool.
+// (A concat input, dec1's 64 + 64 -> 64, goes to the tap-reuse conv in one
+// pass with the whole K = 1152 sum in fp32: the same graph-step time as two
+// streaming passes, profiles/r4j_abstep_concat_splitdgrad.txt, without a bf16
+// rounding of the half sum.)
+S3Pick stream3_pick(const rr_igemm_desc *d, const RrPath &p, int kind) {
+  const S3Pick no = {-1, 0};
+  const int cw = stream3_geom_ok(d, p);
+  if (!cw || d->c_in2) return no;
+  const int strip = cw != d->w;
+  const int f = kind == CK_BNBWD ? F_BNBWD : kind == CK_EX ? s3_ex_flags(d) : s3_flags(d);
+  if (f < 0 || (strip && !s3_strip_flags(f))) return no;
+  switch (kind) {
+    case CK_POOL:   // (the eval judge: no window index)
+      return d->has_bias ? S3Pick{F_BIAS | F_RELU | F_POOL | F_PNOIDX, strip} : no;
+    case CK_POOL_IDX: return strip ? no : S3Pick{f | F_POOL, 0};
+    case CK_DGRAD_SC: return strip || f != 0 ? no : S3Pick{F_SC, 0};
+    case CK_PRE: return strip || f != (F_BIAS | F_STATS) ? no : S3Pick{f | F_PRE, 0};
+    default: return S3Pick{f, strip};
+  }
 }
 
-int stream3_launch_ex(const rr_igemm_desc *d, const S3Args &a0, hipStream_t st) {
-  const int f = s3_ex_flags(d);
-  if (!stream3_ex_ok(d) || f < 0 || !a0.x || !a0.wt || !a0.bias || ((f & F_PRELU) && !a0.alpha) ||
-      ((f & F_RES) && !a0.res) || ((f & F_POOL) && !a0.ypool) || (((f & F_PFULL) || !(f & F_POOL)) && !a0.y))
-    return RR_EUNSUPPORTED;
-  S3Args a = a0;
+// workgroups (= rows of the stats / bnbwd partial slabs): fixed, so the count
+// a caller sizes from the plain descriptor matches every launch
+int stream3_rows() { return S3_WG; }
+
+const char *stream3_name(const rr_igemm_desc *d, S3Pick k, int kind) {
+  static const char *names[3][3] = {
+      {"stream3_kernel<64>", "stream3_kernel<64,pool>", "stream3_kernel<64,sc>"},
+      {"stream3_kernel<32>", "stream3_kernel<32,pool>", "stream3_kernel<32,sc>"},
+      {"stream3_kernel<s32>", "stream3_kernel<s32,pool>", "stream3_kernel<s32,sc>"}};
+  const int c = kind == CK_POOL || kind == CK_POOL_IDX ? 1 : kind == CK_DGRAD_SC ? 2 : 0;
+  return names[k.strip ? 2 : d->w == 64 ? 0 : 1][c];
+}
+
+int stream3_launch(const rr_igemm_desc *d, S3Args a, S3Pick k, hipStream_t st) {
   a.wld = 64; a.woff = 0; a.w = d->w;
   const int P = d->n * d->h * d->w;
-  return s3_go(d, a, f, P, st);
+  if (k.strip) return launch_strips(a, k.flags, P, st);
+  if (d->w == 64) return launch_w<64>(a, k.flags, P, st);
+  return launch_w<32>(a, k.flags, P, st);
 }
 
 #ifdef RR_S3_STAMPS
@@ -1078,59 +1075,3 @@ extern "C" int rr_s3_stamps_read(unsigned long long *host, int n, int clear) {
   return 0;
 }
 #endif
-
-int stream3_launch_sc(const rr_igemm_desc *d, const S3Args &a0, hipStream_t st) {
-  if (!stream3_blocks(d, 0) || d->c_in2 || s3_flags(d, false) != 0 || !a0.xsc || !a0.wsc || s3_is_strip(d))
-    return RR_EUNSUPPORTED;
-  S3Args a = a0;
-  a.wld = 64; a.woff = 0; a.w = d->w;
-  const int P = d->n * d->h * d->w;
-  // 128-pixel steps, no stagger (the plain dgrad's form, launch_w)
-  if (d->w == 64) launch1<64, 2, F_SC, 0>(a, P, st);
-  else launch1<32, 2, F_SC, 0>(a, P, st);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
-}
-
-int stream3_launch_pool(const rr_igemm_desc *d, const S3Args &a0, hipStream_t st) {
-  if (!stream3_blocks(d, 0) || d->c_in2 || d->act != RR_ACT_RELU || d->accumulate || d->has_mask ||
-      d->want_stats || !a0.ypool || (!a0.pidx && !d->has_bias) || (a0.pidx && s3_is_strip(d)))
-    return RR_EUNSUPPORTED;
-  S3Args a = a0;
-  a.wld = 64; a.woff = 0; a.w = d->w;
-  const int P = d->n * d->h * d->w;
-  if (!a0.pidx)   // (the eval judge: no window index)
-    return s3_go(d, a, F_BIAS | F_RELU | F_POOL | F_PNOIDX, P, st);
-  // 128-pixel steps, no stagger: the bias + ReLU forward's form (launch_w;
-  // 256-pixel steps at W = 64 were bitwise equal and within the run order's
-  // noise, profiles/r5zi_pool_bench.jsonl, r5zj_pool_bench.jsonl)
-  if (d->w == 64) {
-    if (d->has_bias) launch1<64, 2, F_BIAS | F_RELU | F_POOL, 0>(a, P, st);
-    else launch1<64, 2, F_RELU | F_POOL, 0>(a, P, st);
-  } else {
-    if (d->has_bias) launch1<32, 2, F_BIAS | F_RELU | F_POOL, 0>(a, P, st);
-    else launch1<32, 2, F_RELU | F_POOL, 0>(a, P, st);
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
-}
-
-int stream3_launch_pre(const rr_igemm_desc *d, const S3Args &a0, hipStream_t st) {
-  if (!stream3_blocks(d, 0) || s3_is_strip(d) || s3_flags(d, false) != (F_BIAS | F_STATS) || !a0.pre_s ||
-      !a0.pre_b || !a0.pre_alpha)
-    return RR_EUNSUPPORTED;
-  S3Args a = a0;
-  a.wld = 64; a.woff = 0; a.w = d->w;
-  const int P = d->n * d->h * d->w;
-  if (d->w == 64) return launch_w<64>(a, F_BIAS | F_STATS | F_PRE, P, st);
-  return launch_w<32>(a, F_BIAS | F_STATS | F_PRE, P, st);
-}
-
-int stream3_launch(const rr_igemm_desc *d, const S3Args &a0, int bnbwd, hipStream_t st) {
-  if (!stream3_blocks(d, bnbwd)) return RR_EUNSUPPORTED;
-  S3Args a = a0;
-  const int P = d->n * d->h * d->w;
-  a.wld = 64; a.woff = 0; a.w = d->w;
-  const int f = s3_flags(d, bnbwd != 0);
-  return s3_go(d, a, f, P, st);
-}

@@ -374,9 +374,9 @@ __global__ __launch_bounds__(512, 2) void swgrad_kernel(SWArgs a) {
 
 static int sw_slices(const rr_wgrad_desc *d) { return (d->c_in1 + d->c_in2) / 64 * (d->c_out / 64); }
 
-int swgrad_ok(const rr_wgrad_desc *d) {
+int swgrad_ok(const rr_wgrad_desc *d, const RrPath &p) {
   // RR_PATH swgrad=0: the halo / tiled weight grads instead (tests)
-  if (!rr_path("swgrad", 1)) return 0;
+  if (!p.swgrad) return 0;
   if (d->dtype != RR_BF16 || d->mode != RR_CONV3X3 || d->c_out % 64 || d->c_out > 128) return 0;
   if (d->w != 64 && d->w != 32) return 0;
   if (d->c_in1 % 64 || d->c_in2 % 64 || d->c_in1 + d->c_in2 > 192 || d->c_in1 <= 0) return 0;
@@ -388,7 +388,8 @@ int swgrad_ok(const rr_wgrad_desc *d) {
 
 int swgrad_nsplit(const rr_wgrad_desc *d) { return SW_WG / sw_slices(d); }
 
-int swgrad_launch(const rr_wgrad_desc *d, const void *dy, const void *x1, const void *x2, void *ws,
+int swgrad_launch(const rr_wgrad_desc *d, const void *dy, const void *x1, const void *x2,
+                  const float *pre_s, const float *pre_b, const float *pre_alpha, void *ws,
                   hipStream_t st) {
   const int S = sw_slices(d);
   SWArgs a;
@@ -403,34 +404,15 @@ int swgrad_launch(const rr_wgrad_desc *d, const void *dy, const void *x1, const 
   a.h = d->h;
   a.nwg_ps = SW_WG / S;
   a.nsteps = (int)((long long)d->n * d->h * d->w / 128);
-  const dim3 grid(a.nwg_ps * S), block(512);
-  a.pre_s = a.pre_b = a.pre_alpha = nullptr;
-  if (d->w == 64) hipLaunchKernelGGL((swgrad_kernel<64, false>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((swgrad_kernel<32, false>), grid, block, 0, st, a);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
-}
-
-int swgrad_launch_pre(const rr_wgrad_desc *d, const void *dy, const void *x1, const float *pre_s,
-                      const float *pre_b, const float *pre_alpha, void *ws, hipStream_t st) {
-  if (!swgrad_ok(d) || d->c_in2 || !pre_s || !pre_b || !pre_alpha) return RR_EUNSUPPORTED;
-  const int S = sw_slices(d);
-  SWArgs a;
-  a.dy = (const char *)dy;
-  a.x1 = (const char *)x1;
-  a.x2 = nullptr;
-  a.c1 = d->c_in1;
-  a.c2 = 0;
-  a.cout = d->c_out;
-  a.partial = (float *)ws;
-  a.n = d->n;
-  a.h = d->h;
-  a.nwg_ps = SW_WG / S;
-  a.nsteps = (int)((long long)d->n * d->h * d->w / 128);
   a.pre_s = pre_s; a.pre_b = pre_b; a.pre_alpha = pre_alpha;
   const dim3 grid(a.nwg_ps * S), block(512);
-  if (d->w == 64) hipLaunchKernelGGL((swgrad_kernel<64, true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((swgrad_kernel<32, true>), grid, block, 0, st, a);
+  if (pre_s) {
+    if (d->w == 64) hipLaunchKernelGGL((swgrad_kernel<64, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((swgrad_kernel<32, true>), grid, block, 0, st, a);
+  } else {
+    if (d->w == 64) hipLaunchKernelGGL((swgrad_kernel<64, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((swgrad_kernel<32, false>), grid, block, 0, st, a);
+  }
   RR_CHECK_LAUNCH();
   return RR_OK;
 }

@@ -709,12 +709,12 @@ int launch_t(const rr_wgrad_desc *d, const Plan &pl, WgradArgs &a, hipStream_t s
 
 }  // namespace
 
-static bool halo_ok(const rr_wgrad_desc *d) {
+static bool halo_ok(const rr_wgrad_desc *d, const RrPath &p) {
   if (d->dtype != RR_BF16 || d->mode != RR_CONV3X3) return false;
   if (!(d->w == 8 || d->w == 16 || d->w == 32 || d->w == 64)) return false;
   if (d->h % (64 / d->w)) return false;
   if (d->c_out % 64 || d->c_in1 % 64 || d->c_in2 % 64) return false;
-  return rr_path("wgrad_halo", 1) != 0;   // RR_PATH wgrad_halo=0: the tiled kernel (tests)
+  return p.wgrad_halo != 0;   // RR_PATH wgrad_halo=0: the tiled kernel (tests)
 }
 
 struct HaloPlan { int stages, split_stages, nsplit; };
@@ -736,114 +736,104 @@ static HaloPlan halo_plan(const rr_wgrad_desc *d) {
   return p;
 }
 
-extern "C" size_t rr_wgrad_workspace(const rr_wgrad_desc *d) {
-  if (!d) return 0;
-  if (swgrad_ok(d))
-    return (size_t)swgrad_nsplit(d) * d->c_out * 9 * (d->c_in1 + d->c_in2) * sizeof(float);
-  if (halo_ok(d)) {
-    const HaloPlan hp = halo_plan(d);
-    return (size_t)hp.nsplit * d->c_out * 9 * (d->c_in1 + d->c_in2) * sizeof(float);
-  }
-  const Plan p = plan_of(d);
-  return (size_t)p.nsplit * p.CA * p.taps * p.CB * sizeof(float);
-}
+// Which kernel one weight-grad call runs and the slabs it leaves: decided
+// once per public call (swgrad -> LDS-halo -> tiled) from the descriptor and
+// the call's RR_PATH snapshot.  The workspace size, the name, the partial
+// launch and the reduce all read the same route.
+enum { WF_SWGRAD, WF_HALO, WF_TILED };
+struct WgradRoute {
+  int family;
+  int CA, CB, taps, nsplit;   // nsplit partial slabs of [CA][taps][CB] fp32
+  int alayout;                // slab layout: 1 [a / 4][tap][b][a % 4] (halo / tiled, CA % 4 == 0), 0 [a][tap][b]
+  size_t ws_bytes;
+  HaloPlan halo;
+  Plan plan;
+  const char *name;           // static string
+};
 
-// the weight-grad kernel rr_wgrad would launch for *d (same decisions;
-// static strings, never NULL)
-extern "C" const char *rr_wgrad_kernel_name(const rr_wgrad_desc *d) {
-  if (!d) return "invalid";
-  if (swgrad_ok(d)) return d->w == 64 ? "swgrad_kernel<64>" : "swgrad_kernel<32>";
-  if (halo_ok(d)) {
-    switch (d->w) {
-      case 64: return "wgrad3_halo_kernel<64>";
-      case 32: return "wgrad3_halo_kernel<32>";
-      case 16: return "wgrad3_halo_kernel<16>";
-      default: return "wgrad3_halo_kernel<8>";
-    }
-  }
-  const Plan pl = plan_of(d);
-  static const char *tn[2][2][2][4] = {
-      {{{"wgrad_kernel<f32,64,64,m0>", "wgrad_kernel<f32,64,64,m1>", "wgrad_kernel<f32,64,64,m2>", "wgrad_kernel<f32,64,64,m3>"},
-        {"wgrad_kernel<f32,64,128,m0>", "wgrad_kernel<f32,64,128,m1>", "wgrad_kernel<f32,64,128,m2>", "wgrad_kernel<f32,64,128,m3>"}},
-       {{"wgrad_kernel<f32,128,64,m0>", "wgrad_kernel<f32,128,64,m1>", "wgrad_kernel<f32,128,64,m2>", "wgrad_kernel<f32,128,64,m3>"},
-        {"wgrad_kernel<f32,128,128,m0>", "wgrad_kernel<f32,128,128,m1>", "wgrad_kernel<f32,128,128,m2>", "wgrad_kernel<f32,128,128,m3>"}}},
-      {{{"wgrad_kernel<bf16,64,64,m0>", "wgrad_kernel<bf16,64,64,m1>", "wgrad_kernel<bf16,64,64,m2>", "wgrad_kernel<bf16,64,64,m3>"},
-        {"wgrad_kernel<bf16,64,128,m0>", "wgrad_kernel<bf16,64,128,m1>", "wgrad_kernel<bf16,64,128,m2>", "wgrad_kernel<bf16,64,128,m3>"}},
-       {{"wgrad_kernel<bf16,128,64,m0>", "wgrad_kernel<bf16,128,64,m1>", "wgrad_kernel<bf16,128,64,m2>", "wgrad_kernel<bf16,128,64,m3>"},
-        {"wgrad_kernel<bf16,128,128,m0>", "wgrad_kernel<bf16,128,128,m1>", "wgrad_kernel<bf16,128,128,m2>", "wgrad_kernel<bf16,128,128,m3>"}}}};
-  const int mi = d->mode >= 0 && d->mode <= 3 ? d->mode : 0;
-  return tn[d->dtype == RR_BF16][pl.BA == 128][pl.BB == 128][mi];
-}
-
-// the reduce of *d's split partials: (CA, CB, taps, nsplit) of the slab
-static void reduce_shape(const rr_wgrad_desc *d, int &CA, int &CB, int &taps, int &nsplit) {
-  if (swgrad_ok(d)) {
-    CA = d->c_out; CB = d->c_in1 + d->c_in2; taps = 9; nsplit = swgrad_nsplit(d);
-  } else if (halo_ok(d)) {
-    CA = d->c_out; CB = d->c_in1 + d->c_in2; taps = 9; nsplit = halo_plan(d).nsplit;
+static WgradRoute wgrad_route(const rr_wgrad_desc *d, const RrPath &p) {
+  WgradRoute r{};
+  r.CA = d->c_out; r.CB = d->c_in1 + d->c_in2; r.taps = 9;
+  if (swgrad_ok(d, p)) {
+    r.family = WF_SWGRAD;
+    r.nsplit = swgrad_nsplit(d);
+    r.name = d->w == 64 ? "swgrad_kernel<64>" : "swgrad_kernel<32>";
+  } else if (halo_ok(d, p)) {
+    r.family = WF_HALO;
+    r.halo = halo_plan(d);
+    r.nsplit = r.halo.nsplit;
+    r.name = d->w == 64 ? "wgrad3_halo_kernel<64>" : d->w == 32 ? "wgrad3_halo_kernel<32>"
+             : d->w == 16 ? "wgrad3_halo_kernel<16>" : "wgrad3_halo_kernel<8>";
   } else {
-    const Plan pl = plan_of(d);
-    CA = pl.CA; CB = pl.CB; taps = pl.taps; nsplit = pl.nsplit;
+    r.family = WF_TILED;
+    r.plan = plan_of(d);
+    r.CA = r.plan.CA; r.CB = r.plan.CB; r.taps = r.plan.taps; r.nsplit = r.plan.nsplit;
+#define TN(ty, tl) {"wgrad_kernel<" ty "," tl ",m0>", "wgrad_kernel<" ty "," tl ",m1>", "wgrad_kernel<" ty "," tl ",m2>", "wgrad_kernel<" ty "," tl ",m3>"}
+    static const char *const tn[2][2][2][4] = {
+        {{TN("f32", "64,64"), TN("f32", "64,128")}, {TN("f32", "128,64"), TN("f32", "128,128")}},
+        {{TN("bf16", "64,64"), TN("bf16", "64,128")}, {TN("bf16", "128,64"), TN("bf16", "128,128")}}};
+#undef TN
+    const int mi = d->mode >= 0 && d->mode <= 3 ? d->mode : 0;
+    r.name = tn[d->dtype == RR_BF16][r.plan.BA == 128][r.plan.BB == 128][mi];
   }
+  r.alayout = r.family != WF_SWGRAD && r.CA % 4 == 0;
+  r.ws_bytes = (size_t)r.nsplit * r.CA * r.taps * r.CB * sizeof(float);
+  return r;
 }
 
-static bool wgrad_desc_ok(const rr_wgrad_desc *d) {
-  return d->mode == RR_CONV3X3 || d->mode == RR_CONV1X1 || d->mode == RR_CONVT_UP;
+extern "C" size_t rr_wgrad_workspace(const rr_wgrad_desc *d) {
+  return d ? wgrad_route(d, rr_path_read()).ws_bytes : 0;
 }
 
-extern "C" int rr_wgrad_reduce(const rr_wgrad_desc *d, const void *ws, size_t ws_bytes, float *dw,
-                               rr_stream stream) {
-  if (!d || !ws || !dw || !wgrad_desc_ok(d)) return RR_EINVAL;
+// the weight-grad kernel rr_wgrad launches for *d (static strings, never NULL)
+extern "C" const char *rr_wgrad_kernel_name(const rr_wgrad_desc *d) {
+  return d ? wgrad_route(d, rr_path_read()).name : "invalid";
+}
+
+static int wgrad_reduce(const rr_wgrad_desc *d, const WgradRoute &r, const void *ws, size_t ws_bytes,
+                        float *dw, hipStream_t st) {
+  if (!ws || !dw || (d->mode != RR_CONV3X3 && d->mode != RR_CONV1X1 && d->mode != RR_CONVT_UP))
+    return RR_EINVAL;
   if (d->c_in1 % 64 || d->c_in2 % 64 || d->c_out % 64) return RR_EUNSUPPORTED;
-  if (ws_bytes < rr_wgrad_workspace(d)) return RR_EWORKSPACE;
-  int CA, CB, taps, nsplit;
-  reduce_shape(d, CA, CB, taps, nsplit);
-  const int alayout = !swgrad_ok(d) && CA % 4 == 0;   // the halo / tiled kernels' slab layout
-  launch_reduce((const float *)ws, dw, CA, CB, taps, nsplit, d->accumulate, alayout, (hipStream_t)stream);
+  if (ws_bytes < r.ws_bytes) return RR_EWORKSPACE;
+  launch_reduce((const float *)ws, dw, r.CA, r.CB, r.taps, r.nsplit, d->accumulate, r.alayout, st);
   RR_CHECK_LAUNCH();
   return RR_OK;
 }
 
-extern "C" int rr_wgrad(const rr_wgrad_desc *d, const void *dy, const void *x1,
-                        const void *x2, float *dw, void *ws, size_t ws_bytes,
-                        rr_stream stream) {
-  if (!dw) return RR_EINVAL;
-  const int rc = rr_wgrad_partial(d, dy, x1, x2, ws, ws_bytes, stream);
-  if (rc) return rc;
-  return rr_wgrad_reduce(d, ws, ws_bytes, dw, stream);
-}
-
-extern "C" int rr_wgrad_pre_ok(const rr_wgrad_desc *d) {
-  return d && d->mode == RR_CONV3X3 && !d->c_in2 && !d->accumulate && swgrad_ok(d) ? 1 : 0;
-}
-
-// conv2's weight grad with BN1 + PReLU of its input folded in: x1 is t1 and
-// the kernel reads PReLU(t1 * pre_scale + pre_shift) (the bytes
-// rr_affine_act(t1, pre_scale, pre_shift, pre_alpha) would store); the
-// partial slabs then go through rr_wgrad_reduce
-extern "C" int rr_wgrad_pre(const rr_wgrad_desc *d, const void *dy, const void *x1,
-                            const float *pre_scale, const float *pre_shift, const float *pre_alpha,
-                            float *dw, void *ws, size_t ws_bytes, rr_stream stream) {
-  if (!d || !dy || !x1 || !dw || !pre_scale || !pre_shift || !pre_alpha) return RR_EINVAL;
-  if (!rr_wgrad_pre_ok(d)) return RR_EUNSUPPORTED;
-  const size_t need = rr_wgrad_workspace(d);
-  if (!ws || ws_bytes < need) return RR_EWORKSPACE;
-  const int rc = swgrad_launch_pre(d, dy, x1, pre_scale, pre_shift, pre_alpha, ws, (hipStream_t)stream);
-  if (rc) return rc;
-  return rr_wgrad_reduce(d, ws, ws_bytes, dw, stream);
-}
-
-extern "C" int rr_wgrad_partial(const rr_wgrad_desc *d, const void *dy, const void *x1,
-                                const void *x2, void *ws, size_t ws_bytes, rr_stream stream) {
-  if (!d || !dy || !x1) return RR_EINVAL;
+// pre_*: the input transform of rr_wgrad_pre (swgrad only), else null
+static int wgrad_partial(const rr_wgrad_desc *d, const WgradRoute &r, const void *dy, const void *x1,
+                         const void *x2, const float *pre_s, const float *pre_b, const float *pre_alpha,
+                         void *ws, size_t ws_bytes, hipStream_t st) {
+  if (!dy || !x1) return RR_EINVAL;
   if (d->mode != RR_CONV3X3 && d->mode != RR_CONV1X1 && d->mode != RR_CONVT_UP) return RR_EINVAL;
   if (d->c_in1 % 64 || d->c_in2 % 64 || d->c_out % 64) return RR_EUNSUPPORTED;
   if (d->c_in2 > 0 && (!x2 || d->mode == RR_CONVT_UP)) return RR_EINVAL;
   const long long P = (long long)d->n * d->h * d->w;
   if (P <= 0 || P * 4 > 0x7fffffffLL) return RR_EUNSUPPORTED;
-  const Plan pl = plan_of(d);
-  const size_t need = rr_wgrad_workspace(d);
-  if (!ws || ws_bytes < need) return RR_EWORKSPACE;
+  if (!ws || ws_bytes < r.ws_bytes) return RR_EWORKSPACE;
+  if (r.family == WF_SWGRAD) return swgrad_launch(d, dy, x1, x2, pre_s, pre_b, pre_alpha, ws, st);
+  if (r.family == WF_HALO) {
+    Halo3Args ha;
+    ha.A = (const char *)dy; ha.B1 = (const char *)x1; ha.B2 = (const char *)x2;
+    ha.partial = (float *)ws;
+    ha.CA = r.CA; ha.CB = r.CB; ha.c1 = d->c_in1; ha.c2 = d->c_in2;
+    ha.n = d->n; ha.h = d->h; ha.w = d->w;
+    ha.lw = __builtin_ctz((unsigned)d->w);
+    ha.stages = r.halo.stages; ha.split_stages = r.halo.split_stages;
+    ha.nablk = ha.CA / 64; ha.nbblk = ha.CB / 64;
+    ha.xcd = 1;                                  // XCD-aware workgroup order
+    const dim3 grid((unsigned)(ha.nablk * ha.nbblk * r.nsplit)), block(256);
+    switch (d->w) {
+      case 64: hipLaunchKernelGGL((wgrad3_halo_kernel<64>), grid, block, 0, st, ha); break;
+      case 32: hipLaunchKernelGGL((wgrad3_halo_kernel<32>), grid, block, 0, st, ha); break;
+      case 16: hipLaunchKernelGGL((wgrad3_halo_kernel<16>), grid, block, 0, st, ha); break;
+      default: hipLaunchKernelGGL((wgrad3_halo_kernel<8>), grid, block, 0, st, ha); break;
+    }
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  }
+  const Plan &pl = r.plan;
   WgradArgs a;
   const bool convT = d->mode == RR_CONVT_UP;
   a.A = (const char *)(convT ? x1 : dy);
@@ -861,33 +851,50 @@ extern "C" int rr_wgrad_partial(const rr_wgrad_desc *d, const void *dy, const vo
   a.xcd = 1;                                   // XCD-aware workgroup order
   a.fd_w = make_fastdiv((uint32_t)d->w);
   a.fd_hw = make_fastdiv((uint32_t)(d->h * d->w));
-  hipStream_t st = (hipStream_t)stream;
-  if (swgrad_ok(d)) {
-    const int rc = swgrad_launch(d, dy, x1, x2, ws, st);
-    if (rc) return rc;
-    RR_CHECK_LAUNCH();
-    return RR_OK;
-  }
-  if (halo_ok(d)) {
-    const HaloPlan hp = halo_plan(d);
-    Halo3Args ha;
-    ha.A = (const char *)dy; ha.B1 = (const char *)x1; ha.B2 = (const char *)x2;
-    ha.partial = (float *)ws;
-    ha.CA = d->c_out; ha.CB = d->c_in1 + d->c_in2; ha.c1 = d->c_in1; ha.c2 = d->c_in2;
-    ha.n = d->n; ha.h = d->h; ha.w = d->w;
-    ha.lw = __builtin_ctz((unsigned)d->w);
-    ha.stages = hp.stages; ha.split_stages = hp.split_stages;
-    ha.nablk = ha.CA / 64; ha.nbblk = ha.CB / 64;
-    ha.xcd = a.xcd;
-    const dim3 grid((unsigned)(ha.nablk * ha.nbblk * hp.nsplit)), block(256);
-    switch (d->w) {
-      case 64: hipLaunchKernelGGL((wgrad3_halo_kernel<64>), grid, block, 0, st, ha); break;
-      case 32: hipLaunchKernelGGL((wgrad3_halo_kernel<32>), grid, block, 0, st, ha); break;
-      case 16: hipLaunchKernelGGL((wgrad3_halo_kernel<16>), grid, block, 0, st, ha); break;
-      default: hipLaunchKernelGGL((wgrad3_halo_kernel<8>), grid, block, 0, st, ha); break;
-    }
-    RR_CHECK_LAUNCH();
-    return RR_OK;
-  }
   return d->dtype == RR_BF16 ? launch_t<bf16_t>(d, pl, a, st) : launch_t<float>(d, pl, a, st);
+}
+
+extern "C" int rr_wgrad_partial(const rr_wgrad_desc *d, const void *dy, const void *x1,
+                                const void *x2, void *ws, size_t ws_bytes, rr_stream stream) {
+  if (!d) return RR_EINVAL;
+  return wgrad_partial(d, wgrad_route(d, rr_path_read()), dy, x1, x2, nullptr, nullptr, nullptr, ws,
+                       ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int rr_wgrad_reduce(const rr_wgrad_desc *d, const void *ws, size_t ws_bytes, float *dw,
+                               rr_stream stream) {
+  if (!d) return RR_EINVAL;
+  return wgrad_reduce(d, wgrad_route(d, rr_path_read()), ws, ws_bytes, dw, (hipStream_t)stream);
+}
+
+extern "C" int rr_wgrad(const rr_wgrad_desc *d, const void *dy, const void *x1,
+                        const void *x2, float *dw, void *ws, size_t ws_bytes,
+                        rr_stream stream) {
+  if (!dw || !d) return RR_EINVAL;
+  const WgradRoute r = wgrad_route(d, rr_path_read());
+  const int rc = wgrad_partial(d, r, dy, x1, x2, nullptr, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream);
+  return rc ? rc : wgrad_reduce(d, r, ws, ws_bytes, dw, (hipStream_t)stream);
+}
+
+static bool wgrad_pre_ok(const rr_wgrad_desc *d, const WgradRoute &r) {
+  return d->mode == RR_CONV3X3 && !d->c_in2 && !d->accumulate && r.family == WF_SWGRAD;
+}
+
+extern "C" int rr_wgrad_pre_ok(const rr_wgrad_desc *d) {
+  return d && wgrad_pre_ok(d, wgrad_route(d, rr_path_read())) ? 1 : 0;
+}
+
+// conv2's weight grad with BN1 + PReLU of its input folded in: x1 is t1 and
+// the kernel reads PReLU(t1 * pre_scale + pre_shift) (the bytes
+// rr_affine_act(t1, pre_scale, pre_shift, pre_alpha) would store); the
+// partial slabs then go through the same reduce
+extern "C" int rr_wgrad_pre(const rr_wgrad_desc *d, const void *dy, const void *x1,
+                            const float *pre_scale, const float *pre_shift, const float *pre_alpha,
+                            float *dw, void *ws, size_t ws_bytes, rr_stream stream) {
+  if (!d || !dy || !x1 || !dw || !pre_scale || !pre_shift || !pre_alpha) return RR_EINVAL;
+  const WgradRoute r = wgrad_route(d, rr_path_read());
+  if (!wgrad_pre_ok(d, r)) return RR_EUNSUPPORTED;
+  const int rc = wgrad_partial(d, r, dy, x1, nullptr, pre_scale, pre_shift, pre_alpha, ws, ws_bytes,
+                               (hipStream_t)stream);
+  return rc ? rc : wgrad_reduce(d, r, ws, ws_bytes, dw, (hipStream_t)stream);
 }

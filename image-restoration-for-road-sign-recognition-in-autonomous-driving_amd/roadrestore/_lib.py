@@ -8,21 +8,29 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RR_LIB_PATH: load another build of the same ABI (A/B of two builds on one box)
 LIB_PATH = os.environ.get("RR_LIB_PATH") or os.path.join(_HERE, "libroadrestore.so")
 
 
-
+# The library reads RR_PATH at every routing call, so a test can switch its
+# keys between calls (monkeypatch.setenv).  The Python-side keys below are
+# read ONCE, at import of the module that holds them (engine._FUSED_POOL,
+# ops._BN_GM_IN_REDUCE, ...): a test that wants another value must patch that
+# module attribute, not the environment.
 def path_flag(key: str, default: int) -> int:
     """The stack's one A/B and test knob, shared with the library
-    (csrc/common.h rr_path): RR_PATH="key=value[,key=value...]".  Every
+    (csrc/common.h rr_path_read): RR_PATH="key=value[,key=value...]".  Every
     default is the measured-best path; the Python schedule reads its fusion
-    keys (fused_pool=0, split_dgrad=0, ...) once at import."""
+    keys (fused_pool=0, split_dgrad=0, ...) with this.  One grammar on both
+    sides: spaces around key and value are ignored, the value is an optional
+    sign and 1-9 decimal digits, an item that is not that is ignored (the
+    default holds), the first valid item of a key wins."""
     for item in os.environ.get("RR_PATH", "").split(","):
         k, sep, v = item.partition("=")
-        if sep and k.strip() == key:
+        if sep and k.strip(" ") == key and re.fullmatch(r"[+-]?[0-9]{1,9}", v.strip(" ")):
             return int(v)
     return default
 
@@ -89,7 +97,7 @@ _SIGS = {
     "rr_igemm_stat_blocks": (I_, [C.POINTER(IgemmDesc)]),
     "rr_igemm_kernel_name": (C.c_char_p, [C.POINTER(IgemmDesc), I_]),
     "rr_igemm_pool": (I_, [C.POINTER(IgemmDesc), P_, P_, P_, P_, P_, P_, P_]),
-    "rr_igemm_pool_kernel_name": (C.c_char_p, [C.POINTER(IgemmDesc)]),
+    "rr_igemm_pool_kernel_name": (C.c_char_p, [C.POINTER(IgemmDesc), I_]),
     "rr_igemm_dgrad_sc": (I_, [C.POINTER(IgemmDesc), P_, P_, P_, P_, I_, P_, P_]),
     "rr_igemm_dgrad_sc_kernel_name": (C.c_char_p, [C.POINTER(IgemmDesc), I_]),
     "rr_igemm_pre_ok": (I_, [C.POINTER(IgemmDesc)]),

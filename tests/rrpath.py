@@ -1,4 +1,4 @@
-"""RR_PATH (csrc/common.h rr_path, roadrestore._lib.path_flag): the one
+"""RR_PATH (csrc/common.h rr_path_read, roadrestore._lib.path_flag): the one
 kernel-path override the parity tests use to check one shipped kernel
 against another on the same shape."""
 import os

@@ -189,6 +189,35 @@ def test_wgrad_partial_reduce_on_another_stream(dev, shape):
         assert torch.equal(got, ref), (shape, acc)
 
 
+@pytest.mark.parametrize("case", [
+    (torch.bfloat16, 8, 64, 64, "swgrad_kernel<64>"),        # the smallest batches the streaming
+    (torch.bfloat16, 32, 32, 32, "swgrad_kernel<32>"),       # weight grad takes (256 128-pixel steps)
+    (torch.bfloat16, 1, 8, 8, "wgrad3_halo_kernel<8>"),
+    (torch.float32, 1, 5, 7, "wgrad_kernel<f32,64,64,m0>"),
+])
+def test_wgrad_partial_reduce_per_family(dev, case):
+    """rr_wgrad_partial + rr_wgrad_reduce == rr_wgrad bit for bit at the
+    smallest 64 -> 64 3x3 shape each weight-grad family takes: the two public
+    calls route separately and must agree on the slab count and layout the
+    one-call form uses"""
+    import roadrestore as rr
+    from roadrestore._lib import RR_CONV3X3, WgradDesc
+    dt, n, h, w, kname = case
+    d = WgradDesc(rr.ops.rr_dtype(dt), RR_CONV3X3, n, h, w, 64, 0, 64, 0)
+    assert rr.ops.wgrad_kernel_name(d) == kname
+    x = nhwc(rnd(n, 64, h, w, seed=71), dev, dt)
+    g = nhwc(rnd(n, 64, h, w, seed=72), dev, dt)
+    side = torch.cuda.Stream(dev)
+    for acc in (False, True):
+        base = rnd(64, 64, 3, 3, seed=73).to(dev)
+        ref = rr.ops.wgrad(RR_CONV3X3, g, x, None, n, h, w, 64, dw=base.clone(), accumulate=acc)
+        got = rr.ops.wgrad(RR_CONV3X3, g, x, None, n, h, w, 64, dw=base.clone(), accumulate=acc,
+                           reduce_stream=side)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        assert torch.equal(got, ref), (case, acc)
+
+
 @pytest.mark.parametrize("hw", [(8, 8), (16, 16), (12, 32), (2, 64), (1, 8, 8), (3, 8, 8), (1, 16, 16)])
 @pytest.mark.parametrize("halo", [True, False])
 def test_wgrad3_halo(dev, hw, halo, monkeypatch):

@@ -45,7 +45,7 @@ def test_igemm_pool_equals_conv_relu_then_pool(dev, case):
     x, wt, b = _mk(n, h, w, c, co, dev, seed=h * 7 + c)
     pk, _ = ops.pack_conv(wt, BF)
     d = ops.igemm_pool_desc(x, n, h, w, co, True)
-    assert ops.igemm_pool_kernel_name(d).startswith(kname), ops.igemm_pool_kernel_name(d)
+    assert ops.igemm_pool_kernel_name(d, True).startswith(kname), ops.igemm_pool_kernel_name(d, True)
     y, _, _ = ops.igemm(RR_CONV3X3, x, None, n, h, w, pk, co, bias=b, act=1)
     ref, ridx = ops.maxpool2_fwd(y)
     yp, idx = ops.igemm_pool(x, n, h, w, pk, co, bias=b)
@@ -92,7 +92,7 @@ def test_perceptual_features_fused_pool_grad_equals_unfused(dev, monkeypatch):
     gx = engine.vgg_features_backward_input(S, gl)
     torch.cuda.synchronize()
     # unfused: pretend rr_igemm_pool supports nothing
-    monkeypatch.setattr(ops, "igemm_pool_kernel_name", lambda d: "unsupported")
+    monkeypatch.setattr(ops, "igemm_pool_kernel_name", lambda d, with_index=True: "unsupported")
     feats2, S2 = engine.vgg_features_forward(perc.slice, x, wc, BF, need_bwd=True)
     assert [k for k, *_ in S2.acts].count("pool") == 2
     gx2 = engine.vgg_features_backward_input(S2, gl)

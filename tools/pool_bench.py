@@ -46,7 +46,7 @@ def main():
         pk, _ = ops.pack_conv(wt, BF)
         y, _, _ = ops.igemm(RR_CONV3X3, x, None, n, h, h, pk, c, bias=b, act=1)
         d = ops.igemm_pool_desc(x, n, h, h, c, True)
-        r = {"shape": [n, h, h, c], "pool_kernel": ops.igemm_pool_kernel_name(d),
+        r = {"shape": [n, h, h, c], "pool_kernel": ops.igemm_pool_kernel_name(d, True),
              "conv_relu_us": timed(lambda: ops.igemm(RR_CONV3X3, x, None, n, h, h, pk, c, bias=b, act=1, out=y)),
              "maxpool_us": timed(lambda: ops.maxpool2_fwd(y)),
              "fused_us": timed(lambda: ops.igemm_pool(x, n, h, h, pk, c, bias=b)),
