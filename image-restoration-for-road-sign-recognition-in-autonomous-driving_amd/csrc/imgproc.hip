@@ -24,6 +24,7 @@
 // Both are HBM-bound byte work: no MFMA, one thread per output pixel (resize)
 // or per output column (SSIM), coalesced along the innermost NHWC axis.
 #include "common.h"
+#include "philox.h"
 
 #include <cmath>
 
@@ -505,16 +506,6 @@ __device__ __forceinline__ unsigned long long dist_seed(const DistCfg &a) {
   return a.seed_dev ? *a.seed_dev : a.seed;
 }
 
-__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3,
-                                             uint32_t k0, uint32_t k1) {
-  const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-  const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-  const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0;
-  const uint32_t h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-  const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-  c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-}
-
 // standard normal for element e (Philox4x32-10, two 24-bit uniforms,
 // Box-Muller in fp32: np.random.normal's stream cannot be reproduced anyway,
 // and the fp32 transcendentals cost a fraction of the fp64 library ones --
@@ -719,16 +710,6 @@ static void launch_blur(const DistCfg &a, long long tp, const RrPath &p, hipStre
 // blur kernel of (degree, angle) is an index into a table of all 11 x 361
 // kernels built once on the host by rr_motion_blur_kernel.
 constexpr int DRAW_DEG0 = 5, DRAW_NDEG = 11, DRAW_NANG = 361;
-
-__device__ __forceinline__ void philox4(uint32_t c[4], unsigned long long key) {
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c[0], c[1], c[2], c[3], k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
 
 __device__ __forceinline__ double u01(uint32_t hi, uint32_t lo) {       // [0, 1), 53 bits
   return ((((unsigned long long)hi << 21) ^ lo) & ((1ull << 53) - 1)) * 0x1p-53;

@@ -190,6 +190,16 @@ _SIGS = {
     "rr_distort_random_u8": (I_, [I_, I_, I_, I_, P_, P_, C.c_ulonglong, P_, P_, P_, S_, P_]),
     "rr_distort_random_draws": (I_, [I_, I_, I_, I_, P_, C.POINTER(S_), C.POINTER(S_),
                                      C.POINTER(S_)]),
+    "rr_linear_wgrad": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, I_, P_]),
+    "rr_linear_dgrad": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, P_]),
+    "rr_dropout_fwd": (I_, [L_, F_, C.c_ulonglong, P_, P_, P_, P_, P_]),
+    "rr_dropout_bwd": (I_, [L_, F_, P_, P_, P_, P_]),
+    "rr_dropout_mask": (I_, [L_, F_, C.c_ulonglong, L_, P_, P_]),
+    "rr_cross_entropy_workspace": (S_, [I_, I_]),
+    "rr_cross_entropy": (I_, [I_, I_, P_, P_, P_, P_, P_, P_, S_, P_]),
+    "rr_softmax_max": (I_, [I_, I_, P_, P_, P_, P_]),
+    "rr_sgd": (I_, [L_, P_, P_, P_, F_, F_, F_, F_, I_, I_, P_]),
+    "rr_sgd_dev": (I_, [L_, P_, P_, P_, P_, F_, F_, F_, I_, P_, I_, P_]),
     "rr_scalar_accumulate": (I_, [P_, P_, P_, P_]),
     "rr_zero": (I_, [P_, S_, P_]),
     "rr_version": (C.c_char_p, []),

@@ -1058,12 +1058,17 @@ def vgg_features_backward_input(S, g_pre_last, x_grad_out=None, accumulate=False
     raise RuntimeError("unreachable")
 
 
+def vgg_pooled_features(vgg, x, wc, dt):
+    """features + avgpool + flatten: [n, 25088] in the compute dtype (NCHW
+    flatten order), the classifier's input"""
+    f, _ = vgg_features_forward(vgg.features, x, wc, dt)
+    return ops.adaptive_avgpool_flatten(f, 7, 7)
+
+
 def vgg_classifier_forward(vgg, x, wc, dt):
     """Eval-mode VGG16 logits (Dropout = identity): 18:46."""
-    f, _ = vgg_features_forward(vgg.features, x, wc, dt)
     n = x.shape[0]
-    pooled = ops.adaptive_avgpool_flatten(f, 7, 7)        # [n, 25088] (NCHW flatten)
-    h = pooled.view(n, 1, 1, -1)
+    h = vgg_pooled_features(vgg, x, wc, dt).view(n, 1, 1, -1)
     cls = [m for m in vgg.classifier if type(m).__name__ == "Linear"]
     for i, lin in enumerate(cls):
         pk = wc.linear(lin.weight, dt)

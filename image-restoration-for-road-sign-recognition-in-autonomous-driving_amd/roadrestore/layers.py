@@ -13,7 +13,9 @@ these ops make that work, on NCHW fp32 tensors in and out like torch.nn:
                                                     statistics + running-stat update; eval)
   rr::prelu / rr::prelu_backward, rr::relu / rr::relu_backward
   rr::max_pool2d / rr::max_pool2d_backward          nn.MaxPool2d(2, 2), floor mode
-  rr::linear, rr::adaptive_avg_pool2d               the VGG16 classifier head (forward only)
+  rr::linear / rr::linear_backward, rr::adaptive_avg_pool2d (forward only)
+  rr::dropout / rr::dropout_backward, rr::cross_entropy / rr::cross_entropy_backward,
+  rr::softmax_max                                   training the VGG16 classifier head
 
 Each op converts to the NHWC compute layout, launches the same HIP kernels
 the fused schedules use (igemm / wgrad, the first-conv and last-conv kernels,
@@ -23,6 +25,7 @@ fallback.  ``dtype`` is the compute dtype code (0 fp32, 1 bf16).
 """
 from __future__ import annotations
 
+import weakref
 from typing import Optional, Tuple
 
 import torch
@@ -458,7 +461,7 @@ max_pool2d.register_autograd(_pool_bwd, setup_context=_pool_setup)
 
 
 # ---------------------------------------------------------------------------
-# the VGG16 classifier head (forward only: the judge is frozen, 18:46)
+# the VGG16 classifier head (18:46 as the frozen judge; 05:59-82 trained)
 
 @torch.library.custom_op("rr::adaptive_avg_pool2d", mutates_args=(), device_types="cuda")
 def adaptive_avg_pool2d(x: Tensor, oh: int, ow: int, dtype: int) -> Tensor:
@@ -475,18 +478,61 @@ def _(x, oh, ow, dtype):
     return x.new_empty((x.shape[0], x.shape[1], oh, ow))
 
 
+def _linear_shape_check(fin, fout):
+    if fin % 64:
+        raise NotImplementedError(f"standalone Linear({fin}, {fout}): in_features must be a "
+                                  "multiple of 64 (VGG16's 25088 / 4096)")
+
+
+# The forward pack of a Linear ([fout][fin] in the compute dtype) is shared by
+# the forward GEMM and the input grad.  A few packs are kept, keyed on the
+# weight's storage, version counter and the fused optimizers' generation, so a
+# frozen judge packs once and a trained one re-packs after every step.  While
+# a HIP graph is captured the forward always re-packs (replays must read the
+# weights of their own step) and hands that pack to the backward of the same
+# capture.
+_PACKS: dict = {}
+_PACKS_MAX = 6
+
+
+def _linear_pack(weight, dt, forward):
+    from .optim import GENERATION
+    cap = torch.cuda.is_current_stream_capturing()
+    key = (weight.data_ptr(), tuple(weight.shape), dt, cap)
+    ver = (weight._version, GENERATION[0])
+    e = _PACKS.get(key)
+    if e is not None and e[0] == ver and not (cap and forward):
+        if cap:
+            _forget_pack(key)
+        return e[1]
+    fout, fin = weight.shape
+    pk, _ = ops.pack_conv(weight.contiguous().view(fout, fin, 1, 1), dt, fwd=True, dgrad=False)
+    if forward or not cap:
+        _forget_pack(key)
+        while len(_PACKS) >= _PACKS_MAX:
+            _forget_pack(next(iter(_PACKS)))
+        # the entry goes with the weight tensor: its address can then be
+        # handed to another weight of the same shape and version
+        _PACKS[key] = (ver, pk, weakref.finalize(weight, _PACKS.pop, key, None))
+    return pk
+
+
+def _forget_pack(key):
+    e = _PACKS.pop(key, None)
+    if e is not None:
+        e[2].detach()          # one live finalizer per entry
+
+
 @torch.library.custom_op("rr::linear", mutates_args=(), device_types="cuda")
 def linear(x: Tensor, weight: Tensor, bias: Tensor, dtype: int) -> Tensor:
     """nn.Linear.forward on [N, in] fp32 (a 1x1 implicit GEMM on a 1x1 map)"""
     dt = _TD[dtype]
     n, fin = x.shape
     fout = weight.shape[0]
-    if fin % 64:
-        raise NotImplementedError(f"standalone Linear({fin}, {fout}): in_features must be a "
-                                  "multiple of 64 (VGG16's 25088 / 4096)")
+    _linear_shape_check(fin, fout)
     if n == 0:
         return x.new_empty((0, fout))
-    pk, _ = ops.pack_conv(weight.contiguous().view(fout, fin, 1, 1), dt, fwd=True, dgrad=False)
+    pk = _linear_pack(weight, dt, forward=True)
     xv = x.contiguous().to(dt).view(n, 1, 1, fin)
     y, _, _ = ops.igemm(RR_CONV1X1, xv, None, n, 1, 1, pk, fout, bias=bias.contiguous())
     return y.view(n, fout).float()
@@ -497,6 +543,146 @@ def _(x, weight, bias, dtype):
     return x.new_empty((x.shape[0], weight.shape[0]))
 
 
+@torch.library.custom_op("rr::linear_backward", mutates_args=(), device_types="cuda")
+def linear_backward(grad: Tensor, x: Tensor, weight: Tensor, need_dx: bool,
+                    dtype: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dx, dweight, dbias) of rr::linear; without ``need_dx`` the input grad
+    is not computed and dx is an empty tensor (classifier[0]'s 25088-wide one)"""
+    dt = _TD[dtype]
+    n, fin = x.shape
+    fout = weight.shape[0]
+    _linear_shape_check(fin, fout)
+    dev = x.device
+    if n == 0:
+        return (x.new_zeros((0, fin) if need_dx else (0,)), torch.zeros_like(weight),
+                torch.zeros(fout, dtype=torch.float32, device=dev))
+    g = grad.contiguous().to(dt)
+    dw, db = ops.linear_wgrad(g, x.contiguous().to(dt))
+    if not need_dx:
+        return x.new_empty((0,)), dw, db
+    dx = ops.linear_dgrad(g, _linear_pack(weight, dt, forward=False), fin)
+    return dx, dw, db
+
+
+@linear_backward.register_fake
+def _(grad, x, weight, need_dx, dtype):
+    return (torch.empty_like(x) if need_dx else x.new_empty((0,)), torch.empty_like(weight),
+            weight.new_empty((weight.shape[0],)))
+
+
+def _linear_setup(ctx, inputs, output):
+    x, weight, bias, dtype = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.dtype = dtype
+
+
+def _linear_bwd(ctx, g):
+    x, weight = ctx.saved_tensors
+    need_dx = ctx.needs_input_grad[0]
+    dx, dw, db = torch.ops.rr.linear_backward(g, x, weight, need_dx, ctx.dtype)
+    return (dx if need_dx else None, dw if ctx.needs_input_grad[1] else None,
+            db if ctx.needs_input_grad[2] else None, None)
+
+
+linear.register_autograd(_linear_bwd, setup_context=_linear_setup)
+
+
+# ---------------------------------------------------------------------------
+# training-mode Dropout, CrossEntropyLoss, the softmax confidence (05:59-82,
+# 13:87-92).  The dropout op advances its module's device step counter (module
+# state, as the BatchNorm op above).
+
+@torch.library.custom_op("rr::dropout", mutates_args=(), device_types="cuda")
+def dropout(x: Tensor, p: float, seed: int, module: int) -> Tuple[Tensor, Tensor]:
+    """training-mode nn.Dropout(p) -> (y, byte keep mask); the draw is keyed by
+    (seed, the module's step counter), which advances by one"""
+    mod = _bn_module(module)
+    if x.numel() == 0:
+        return torch.empty_like(x), torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    return ops.dropout_fwd(x.float().contiguous(), p, seed, mod._step_tensor(x.device))
+
+
+@dropout.register_fake
+def _(x, p, seed, module):
+    return torch.empty_like(x), x.new_empty(x.shape, dtype=torch.uint8)
+
+
+@torch.library.custom_op("rr::dropout_backward", mutates_args=(), device_types="cuda")
+def dropout_backward(grad: Tensor, mask: Tensor, p: float) -> Tensor:
+    if grad.numel() == 0:
+        return torch.zeros_like(grad)
+    return ops.dropout_bwd(grad.float().contiguous(), mask, p)
+
+
+@dropout_backward.register_fake
+def _(grad, mask, p):
+    return torch.empty_like(grad)
+
+
+def _dropout_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.p = inputs[1]
+    ctx.mark_non_differentiable(output[1])
+
+
+def _dropout_bwd(ctx, g, g_mask):
+    (mask,) = ctx.saved_tensors
+    return torch.ops.rr.dropout_backward(g, mask, ctx.p), None, None, None
+
+
+dropout.register_autograd(_dropout_bwd, setup_context=_dropout_setup)
+
+
+@torch.library.custom_op("rr::cross_entropy", mutates_args=(), device_types="cuda")
+def cross_entropy(logits: Tensor, target: Tensor) -> Tensor:
+    """nn.CrossEntropyLoss() (mean) of [n, k] fp32 logits and int64 targets;
+    a target outside [0, k) gives a NaN loss (and a zero gradient row)"""
+    return ops.cross_entropy(logits.float(), target)[0]
+
+
+@cross_entropy.register_fake
+def _(logits, target):
+    return logits.new_empty((), dtype=torch.float32)
+
+
+@torch.library.custom_op("rr::cross_entropy_backward", mutates_args=(), device_types="cuda")
+def cross_entropy_backward(grad: Tensor, logits: Tensor, target: Tensor) -> Tensor:
+    """grad * (softmax - onehot) / n"""
+    return ops.cross_entropy(logits.float(), target, want_grad=True,
+                             gscale=grad.float().contiguous())[1]
+
+
+@cross_entropy_backward.register_fake
+def _(grad, logits, target):
+    return torch.empty_like(logits, dtype=torch.float32)
+
+
+def _ce_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+
+
+def _ce_bwd(ctx, g):
+    logits, target = ctx.saved_tensors
+    return torch.ops.rr.cross_entropy_backward(g, logits, target), None
+
+
+cross_entropy.register_autograd(_ce_bwd, setup_context=_ce_setup)
+
+
+@torch.library.custom_op("rr::softmax_max", mutates_args=(), device_types="cuda")
+def softmax_max(logits: Tensor) -> Tuple[Tensor, Tensor]:
+    """torch.max(torch.softmax(logits, 1), 1): (confidence, index), first index
+    on ties (13:87-92)"""
+    return ops.softmax_max(logits.float())
+
+
+@softmax_max.register_fake
+def _(logits):
+    n = logits.shape[0]
+    return logits.new_empty((n,), dtype=torch.float32), logits.new_empty((n,), dtype=torch.int64)
+
+
 OPS = ["conv2d", "conv2d_backward", "conv_transpose2d", "conv_transpose2d_backward",
        "batch_norm", "batch_norm_backward", "prelu", "prelu_backward", "relu", "relu_backward",
-       "max_pool2d", "max_pool2d_backward", "adaptive_avg_pool2d", "linear"]
+       "max_pool2d", "max_pool2d_backward", "adaptive_avg_pool2d", "linear", "linear_backward",
+       "dropout", "dropout_backward", "cross_entropy", "cross_entropy_backward", "softmax_max"]

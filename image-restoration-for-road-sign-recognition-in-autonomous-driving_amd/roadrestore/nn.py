@@ -10,6 +10,7 @@ unchanged):
   VGGPerceptualLoss()       14_train_unified_advanced.py:189-196
   vgg16(num_classes=43)     torchvision cfg "D" + 05:53-54 head swap
   L1Loss / MSELoss          14:219 / 07:142
+  CrossEntropyLoss          05:59
 
 Leaf modules (Conv2d, BatchNorm2d, PReLU, ...) carry the torch.nn default
 initialisation and, called on their own, run one HIP op each
@@ -25,6 +26,7 @@ per-model attribute, ``model.compute_dtype``, or ``RR_COMPUTE_DTYPE``.
 """
 from __future__ import annotations
 
+import itertools
 import math
 import os
 
@@ -37,7 +39,7 @@ from . import torch_ops as _tops
 
 __all__ = ["Conv2d", "ConvTranspose2d", "BatchNorm2d", "PReLU", "ReLU", "MaxPool2d", "Linear",
            "Dropout", "AdaptiveAvgPool2d", "SimpleUNet", "ResidualBlock", "ResUNet",
-           "VGG", "vgg16", "VGGPerceptualLoss", "L1Loss", "MSELoss", "unified_loss",
+           "VGG", "vgg16", "VGGPerceptualLoss", "L1Loss", "MSELoss", "CrossEntropyLoss", "unified_loss",
            "default_compute_dtype"]
 
 
@@ -178,13 +180,10 @@ class Linear(_Leaf):
         tnn.init.uniform_(self.bias, -b, b)
 
     def forward(self, x):
-        """forward only (the VGG16 head is the frozen judge, 18:46)"""
+        """nn.Linear on [..., in] (05:53-54's head; differentiable: rr::linear
+        carries the weight / bias / input grads)"""
         if not x.is_cuda:
             raise RuntimeError("roadrestore layers run on the GPU only (no CPU fallback)")
-        if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad
-                                        or self.bias.requires_grad):
-            raise NotImplementedError("Linear runs forward-only (frozen VGG16 judge): use "
-                                      "torch.no_grad() or freeze its parameters")
         lead = x.shape[:-1]
         y = torch.ops.rr.linear(x.float().reshape(-1, x.shape[-1]), self.weight, self.bias,
                                 self._dt())
@@ -192,16 +191,68 @@ class Linear(_Leaf):
 
 
 class Dropout(_Leaf):
+    """nn.Dropout.  Training mode draws its mask on the device from
+    Philox4x32-10 keyed by (``seed``, a device step counter): the counter
+    advances by one per training forward, also inside a HIP-graph replay, so
+    no host state is read.  ``seed`` is set at the first training call from
+    ``torch.initial_seed()`` and the instance's ordinal in the process (the
+    constructor draws nothing from torch's generator), and may be assigned;
+    ``reset_step(k)`` rewinds the counter (same seed and step: same mask)."""
+
+    _ORDINAL = itertools.count()
+
     def __init__(self, p=0.5):
         super().__init__()
+        if p < 0 or p > 1:
+            raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
         self.p = p
+        self.seed = None
+        self._ordinal = next(Dropout._ORDINAL)
+        self._step = None           # 1-element int64 device tensor, made at the first use
+        self._step_init = 0
+
+    def _step_tensor(self, device):
+        if self._step is None or self._step.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Dropout: run one training forward (or reset_step) on this "
+                                   "device before capturing a HIP graph")
+            k = self._step_init if self._step is None else int(self._step.item())
+            self._step = torch.full((1,), k, dtype=torch.int64, device=device)
+        return self._step
+
+    def reset_step(self, k=0, device=None):
+        """set the step counter (the next training forward draws mask ``k``)"""
+        if device is not None:
+            self._step = None
+            self._step_init = int(k)
+            self._step_tensor(torch.device(device))
+        elif self._step is None:
+            self._step_init = int(k)
+        else:
+            self._step.fill_(int(k))
+
+    def step_count(self):
+        """the counter's value (synchronises)"""
+        return self._step_init if self._step is None else int(self._step.item())
 
     def forward(self, x):
-        """eval (the judge, 18:46): the identity.  Training-mode dropout
-        (VGG16 training, 05) is out of scope."""
-        if self.training and self.p > 0:
-            raise NotImplementedError("training-mode Dropout is out of scope (eval: identity)")
-        return x
+        return self._run(x, self.training)
+
+    def _run(self, x, training):
+        """eval (the judge, 18:46) or p == 0: the identity, ``x`` itself"""
+        if not training or self.p == 0:
+            return x
+        if not x.is_cuda:
+            raise NotImplementedError("training-mode Dropout: roadrestore layers run on the GPU "
+                                      "only (no CPU fallback)")
+        if self.p >= 1:
+            raise NotImplementedError("Dropout(p=1)")
+        if self.seed is None:
+            self.seed = (torch.initial_seed() + 0x9E3779B97F4A7C15 * (self._ordinal + 1)) % (1 << 63)
+        self._step_tensor(x.device)
+        # registered per call: a copy.deepcopy of the module is its own object
+        return torch.ops.rr.dropout(x.float(), float(self.p), int(self.seed) % (1 << 63),
+                                    _tops.register_module(self))[0]
 
 
 class AdaptiveAvgPool2d(_Leaf):
@@ -458,11 +509,39 @@ class VGG(tnn.Module):
         self._op_key = _tops.register_module(self)
 
     def forward(self, x):
-        """Eval-mode logits (18:46): the classifier is the fixed judge."""
+        """Logits.  Three routes:
+
+        * nothing requires grad, or ``torch.no_grad()``: the frozen judge's
+          one fused schedule (18:46).  It computes EVAL-mode logits also when
+          the module was left in training mode -- Dropout acts only where a
+          gradient can flow (the route below);
+        * grad mode with only ``classifier.*`` parameters requiring grad
+          (transfer learning, the option 05:49-50 names): features + avgpool
+          run through that fused schedule without a graph, then the classifier
+          through the differentiable ops (rr::linear, rr::relu, rr::dropout),
+          Dropout active iff ``self.training``;
+        * a ``features.*`` parameter or the input requiring grad: not
+          implemented (the conv weight grads at the VGG geometries)."""
         if not x.is_cuda:
             raise RuntimeError("roadrestore networks run on the GPU only (no CPU fallback)")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("VGG16 runs as the frozen judge: use torch.no_grad()")
+            if x.requires_grad or any(p.requires_grad for p in self.features.parameters()):
+                raise NotImplementedError(
+                    "VGG16 trains its classifier head over frozen features only: freeze the "
+                    "features (for p in vgg.features.parameters(): p.requires_grad = False) and "
+                    "pass an input that does not require grad")
+            with torch.no_grad():
+                h = engine.vgg_pooled_features(self, x.float().contiguous(), self._wc,
+                                               self.compute_dtype).float()
+            dt = _layers.dtype_code(self.compute_dtype)
+            for m in self.classifier:
+                if isinstance(m, Linear):
+                    h = torch.ops.rr.linear(h, m.weight, m.bias, dt)
+                elif isinstance(m, Dropout):
+                    h = m._run(h, self.training)
+                else:
+                    h = m(h)
+            return h
         return torch.ops.rr.vgg16_logits(x.float().contiguous(), list(self.parameters()),
                                          self._op_key)
 
@@ -545,6 +624,17 @@ class VGGPerceptualLoss(tnn.Module):
         y = y.float().contiguous()
         need = torch.is_grad_enabled() and x.requires_grad
         return torch.ops.rr.perceptual_loss(x, y, self._op_key, need)[0]
+
+
+class CrossEntropyLoss(tnn.Module):
+    """nn.CrossEntropyLoss() (mean reduction, class-index targets; 05:59) on
+    device tensors.  A target outside [0, classes) gives a NaN loss and a zero
+    gradient row instead of torch's device assert."""
+
+    def forward(self, logits, target):
+        if not logits.is_cuda:
+            raise RuntimeError("roadrestore losses run on the GPU only (no CPU fallback)")
+        return torch.ops.rr.cross_entropy(logits.float().contiguous(), target.contiguous())
 
 
 class L1Loss(tnn.Module):

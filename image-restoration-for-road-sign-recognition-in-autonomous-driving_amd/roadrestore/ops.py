@@ -23,7 +23,8 @@ __all__ = [
     "loss_fwd", "loss_bwd", "adamw_", "to_uint8_hwc", "psnr_u8", "argmax_rows",
     "adaptive_avgpool_flatten", "zero_", "resize_bilinear_u8", "ssim_u8", "distort_u8",
     "motion_blur_kernel", "first_conv_wgrad_act", "affine_act_pool", "nearest_resize",
-    "nearest_resize_bwd", "fold_conv_bn", "bn_stats",
+    "nearest_resize_bwd", "fold_conv_bn", "bn_stats", "linear_wgrad", "linear_dgrad",
+    "dropout_fwd", "dropout_bwd", "dropout_mask", "cross_entropy", "softmax_max", "sgd_",
 ]
 
 
@@ -1147,6 +1148,139 @@ def distort_u8(x, params, taps, mode=0, noise=None, seed=0):
 def zero_(t):
     lib().check(lib().rr_zero(_p(t), t.numel() * t.element_size(), stream()), "rr_zero")
     return t
+
+
+# ---------------------------------------------------------------------------
+# the classifier head's training ops (05:59-82)
+
+def _f32c(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError(f"{what} must be a contiguous fp32 tensor")
+    return t
+
+
+def linear_wgrad(dy, x, dw=None, db=None, accumulate=False, want_db=True):
+    """nn.Linear's (dweight [fout][fin] fp32, dbias [fout] fp32) from dy [n][fout]
+    and x [n][fin] in one compute dtype; ``dw`` / ``db`` given: written (or
+    added to, ``accumulate``) in place."""
+    _need_cuda(dy, x, dw, db)
+    if dy.dtype != x.dtype or dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:
+        raise ValueError("linear_wgrad: dy [n, fout] and x [n, fin] of one dtype")
+    n, fout = dy.shape
+    fin = x.shape[1]
+    dy, x = dy.contiguous(), x.contiguous()
+    if dw is None:
+        dw = torch.empty((fout, fin), dtype=torch.float32, device=x.device)
+    elif tuple(dw.shape) != (fout, fin):
+        raise ValueError("linear_wgrad: dw must be [fout, fin]")
+    if db is None and want_db:
+        db = torch.empty(fout, dtype=torch.float32, device=x.device)
+    elif db is not None and db.numel() != fout:
+        raise ValueError("linear_wgrad: db must be [fout]")
+    _f32c(dw, "dw")
+    if db is not None:
+        _f32c(db, "db")
+    lib().check(lib().rr_linear_wgrad(rr_dtype(x.dtype), n, fin, fout, _p(dy), _p(x), _p(dw), _p(db),
+                                      int(accumulate), stream()), "rr_linear_wgrad")
+    return dw, db
+
+
+def linear_dgrad(dy, wpack, fin, mask=None, dx=None):
+    """nn.Linear's input grad dy W (fp32) from the layer's FORWARD pack (pack_conv of
+    the [fout, fin, 1, 1] weight); ``mask``: zeroed where mask <= 0 (a ReLU in
+    front of the layer)."""
+    _need_cuda(dy, wpack, mask, dx)
+    n, fout = dy.shape
+    if wpack.dtype != dy.dtype or wpack.numel() < fout * fin:
+        raise ValueError("linear_dgrad: the pack must hold [fout][fin] in dy's dtype")
+    dy = dy.contiguous()
+    if dx is None:
+        dx = torch.empty((n, fin), dtype=torch.float32, device=dy.device)
+    elif tuple(dx.shape) != (n, fin) or dx.dtype != torch.float32 or not dx.is_contiguous():
+        raise ValueError("linear_dgrad: dx must be a contiguous fp32 [n, fin] tensor")
+    if mask is not None and (tuple(mask.shape) != (n, fin) or mask.dtype != torch.float32
+                             or not mask.is_contiguous()):
+        raise ValueError("linear_dgrad: mask must be fp32 in dx's layout")
+    lib().check(lib().rr_linear_dgrad(rr_dtype(dy.dtype), n, fin, fout, _p(dy), _p(wpack), _p(mask),
+                                      _p(dx), stream()), "rr_linear_dgrad")
+    return dx
+
+
+def _seed64(seed):
+    return int(seed) & (2 ** 64 - 1)
+
+
+def dropout_fwd(x, p, seed, step_dev):
+    """training-mode nn.Dropout(p) of an fp32 tensor -> (y, byte keep mask);
+    ``step_dev`` (1-element int64 device tensor) advances by one"""
+    _need_cuda(x, step_dev)
+    x = _f32c(x.contiguous(), "x")
+    if step_dev.dtype != torch.int64 or step_dev.numel() != 1:
+        raise TypeError("dropout_fwd: step_dev is a 1-element int64 device tensor")
+    y = torch.empty_like(x)
+    mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    lib().check(lib().rr_dropout_fwd(x.numel(), float(p), _seed64(seed), _p(step_dev), _p(x), _p(y),
+                                     _p(mask), stream()), "rr_dropout_fwd")
+    return y, mask
+
+
+def dropout_bwd(g, mask, p):
+    _need_cuda(g, mask)
+    g = _f32c(g.contiguous(), "g")
+    dx = torch.empty_like(g)
+    lib().check(lib().rr_dropout_bwd(g.numel(), float(p), _p(g), _p(mask.contiguous()), _p(dx),
+                                     stream()), "rr_dropout_bwd")
+    return dx
+
+
+def dropout_mask(shape, p, seed, step, device):
+    """the byte keep mask dropout_fwd draws at counter value ``step``"""
+    out = torch.empty(shape, dtype=torch.uint8, device=device)
+    _need_cuda(out)
+    lib().check(lib().rr_dropout_mask(out.numel(), float(p), _seed64(seed), int(step), _p(out),
+                                      stream()), "rr_dropout_mask")
+    return out
+
+
+def _ce_args(logits, target):
+    _need_cuda(logits, target)
+    if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
+        raise ValueError("cross_entropy: logits [n, k] and target [n]")
+    if target.dtype != torch.int64:
+        raise TypeError("cross_entropy: target must be int64 class indices")
+    return _f32c(logits.contiguous(), "logits"), target.contiguous()
+
+
+def cross_entropy(logits, target, want_grad=False, gscale=None):
+    """nn.CrossEntropyLoss() (mean) -> (loss scalar, dlogits or None);
+    ``gscale``: a device scalar multiplied into dlogits"""
+    logits, target = _ce_args(logits, target)
+    n, k = logits.shape
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    wsb = lib().rr_cross_entropy_workspace(n, k)
+    ws = _ws(wsb, logits.device)
+    lib().check(lib().rr_cross_entropy(n, k, _p(logits), _p(target), _p(loss), _p(dl), _p(gscale),
+                                       _p(ws), ws.numel(), stream()), "rr_cross_entropy")
+    return loss, dl
+
+
+def softmax_max(logits):
+    """torch.max(torch.softmax(logits, 1), 1) -> (confidence fp32 [n], index int64 [n])"""
+    _need_cuda(logits)
+    logits = _f32c(logits.contiguous(), "logits")
+    n, k = logits.shape
+    conf = torch.empty(n, dtype=torch.float32, device=logits.device)
+    pred = torch.empty(n, dtype=torch.int64, device=logits.device)
+    lib().check(lib().rr_softmax_max(n, k, _p(logits), _p(conf), _p(pred), stream()),
+                "rr_softmax_max")
+    return conf, pred
+
+
+def sgd_(param, grad, buf, lr, momentum, dampening, weight_decay, nesterov, first_step):
+    lib().check(lib().rr_sgd(param.numel(), _p(param), _p(grad), _p(buf), float(lr), float(momentum),
+                             float(dampening), float(weight_decay), int(nesterov), int(first_step),
+                             stream()), "rr_sgd")
 
 
 MODES = dict(conv3x3=RR_CONV3X3, conv1x1=RR_CONV1X1, convT_up=RR_CONVT_UP,

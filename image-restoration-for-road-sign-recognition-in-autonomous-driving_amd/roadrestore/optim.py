@@ -1,4 +1,4 @@
-"""Fused Adam / AdamW (one HIP launch per contiguous parameter span).
+"""Fused Adam / AdamW / SGD (one HIP launch per contiguous parameter span).
 
 Update rule = torch.optim.Adam / AdamW (the reference's optimisers, 07:143 and
 14:222): decoupled weight decay p *= 1 - lr*wd (AdamW), m.lerp_(g, 1-b1),
@@ -78,11 +78,13 @@ def _span(tensors):
     return items
 
 
-class _FusedAdamBase(torch.optim.Optimizer):
-    decoupled = True
+class _FusedBase(torch.optim.Optimizer):
+    """What the fused optimizers share: the per-group state, the device lr
+    tensor of the capturable form, the flat-span test and the version bump."""
 
-    def __init__(self, params, lr, betas, eps, weight_decay, capturable=False):
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+    _name = "a fused optimizer"
+
+    def __init__(self, params, defaults, capturable=False):
         super().__init__(params, defaults)
         self._gstate = {}
         # capturable: the step count and the learning rate live on the device
@@ -132,6 +134,54 @@ class _FusedAdamBase(torch.optim.Optimizer):
                 g["lr"] = float(g["lr"].item())
         return sd
 
+    def _begin_group(self, group):
+        """(params with a grad, group index, group state, step number, param
+        span, grad span) of one group's step; the spans are None unless the
+        parameters and their gradients each tile one contiguous fp32 span in
+        the same order"""
+        ps = [p for p in group["params"] if p.grad is not None]
+        if not ps:
+            return None
+        if any(not p.is_cuda for p in ps):
+            raise RuntimeError(f"{self._name} runs on the GPU only")
+        gi = self.param_groups.index(group)
+        gstate = self._gstate.setdefault(gi, {})
+        gstate["step"] = gstate.get("step", 0) + 1
+        pspan = _span([p.data for p in ps])
+        gspan = _span([p.grad for p in ps]) if pspan is not None else None
+        if pspan is None or gspan is None or [i for _, i in pspan] != [i for _, i in gspan]:
+            pspan = gspan = None
+        return ps, gi, gstate, gstate["step"], pspan, gspan
+
+    def _step_dev(self, gstate, step, device):
+        """the group's device step counter (capturable form), made on the
+        first eager step; it holds the number of steps taken before this one"""
+        if "step_dev" not in gstate:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._name}: take one eager step() before capturing a "
+                                   "HIP graph (the device step counter is made there)")
+            gstate["step_dev"] = torch.full((1,), step - 1, dtype=torch.int64, device=device)
+        if torch.cuda.is_current_stream_capturing():
+            gstate["captured"] = True
+        return gstate["step_dev"]
+
+    def _finish_group(self, ps, step):
+        for p in ps:
+            self.state.setdefault(p, {})["step"] = step
+        # the fused kernel wrote through raw pointers: bump the version
+        # counters so packed-weight caches (engine.WeightCache) and autograd
+        # see the in-place update
+        _bump_versions([p.data for p in ps])
+
+
+class _FusedAdamBase(_FusedBase):
+    decoupled = True
+    _name = "fused Adam/AdamW"
+
+    def __init__(self, params, lr, betas, eps, weight_decay, capturable=False):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super().__init__(params, defaults, capturable)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -139,20 +189,12 @@ class _FusedAdamBase(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         for group in self.param_groups:
-            ps = [p for p in group["params"] if p.grad is not None]
-            if not ps:
+            begun = self._begin_group(group)
+            if begun is None:
                 continue
-            if any(not p.is_cuda for p in ps):
-                raise RuntimeError("fused Adam/AdamW runs on the GPU only")
+            ps, gi, gstate, step, pspan, gspan = begun
             b1, b2 = group["betas"]
-            gi = self.param_groups.index(group)
-            gstate = self._gstate.setdefault(gi, {})
-            gstate["step"] = gstate.get("step", 0) + 1
-            step = gstate["step"]
-            pspan = _span([p.data for p in ps])
-            gspan = _span([p.grad for p in ps]) if pspan is not None else None
-            flat_ok = (pspan is not None and gspan is not None and
-                       [i for _, i in pspan] == [i for _, i in gspan])
+            flat_ok = pspan is not None
             if flat_ok:
                 key = tuple(id(ps[i]) for _, i in pspan)
                 if gstate.get("key") != key:
@@ -198,12 +240,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
                     ops.adamw_(p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"],
                                group["lr"], b1, b2, group["eps"], group["weight_decay"],
                                self.decoupled, step)
-            for p in ps:
-                self.state.setdefault(p, {})["step"] = step
-            # the fused kernel wrote through raw pointers: bump the version
-            # counters so packed-weight caches (engine.WeightCache) and autograd
-            # see the in-place update
-            _bump_versions([p.data for p in ps])
+            self._finish_group(ps, step)
         return loss
 
 
@@ -225,6 +262,101 @@ class Adam(_FusedAdamBase):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  capturable=False):
         super().__init__(params, lr, betas, eps, weight_decay, capturable)
+
+
+class SGD(_FusedBase):
+    """torch.optim.SGD semantics (05:60: lr 1e-3, momentum 0.9): g += wd p;
+    buf = g on a parameter's first step, then momentum buf + (1 - dampening) g;
+    nesterov: g + momentum buf; p -= lr (...).  ``momentum_buffer`` is the
+    state key, as torch's.  One launch per contiguous span (flattened
+    parameters with a flat gradient), else one per parameter.
+
+    ``capturable=True``: lr and the step count live on the device
+    (``rr_sgd_dev``), per parameter too, so the un-flattened classifier head
+    of the VGG16 judge can be captured; take one eager step first."""
+
+    _name = "fused SGD"
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False,
+                 capturable=False):
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening,
+                        weight_decay=weight_decay, nesterov=nesterov)
+        super().__init__(params, defaults, capturable)
+
+    def _launch(self, group, gstate, gi, count, p_ptr, g_ptr, buf, first, advance, device):
+        mu, damp = float(group["momentum"]), float(group["dampening"])
+        wd, nest = float(group["weight_decay"]), int(bool(group["nesterov"]))
+        if self.capturable:
+            lib().check(lib().rr_sgd_dev(
+                count, p_ptr, g_ptr, ops._p(buf), self._lr_to_device(gi, group).data_ptr(), mu, damp,
+                wd, nest, gstate["step_dev"].data_ptr(), int(advance), ops.stream()), "rr_sgd_dev")
+        else:
+            lib().check(lib().rr_sgd(count, p_ptr, g_ptr, ops._p(buf), float(group["lr"]), mu, damp,
+                                     wd, nest, int(first), ops.stream()), "rr_sgd")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            begun = self._begin_group(group)
+            if begun is None:
+                continue
+            ps, gi, gstate, step, pspan, gspan = begun
+            dev = ps[0].device
+            use_buf = group["momentum"] != 0
+            if self.capturable:
+                # one counter per group: a parameter joining later (its first
+                # grad) would need its own "first step", which a captured
+                # launch cannot know
+                self._step_dev(gstate, step, dev)
+                if use_buf and step > 1 and pspan is None and \
+                        any("momentum_buffer" not in self.state.get(p, {}) for p in ps):
+                    raise RuntimeError("capturable SGD: every parameter of a group must have a "
+                                       "gradient from the group's first step on")
+            if pspan is not None:
+                key = tuple(id(ps[i]) for _, i in pspan)
+                first = gstate.get("key") != key
+                if first and use_buf:
+                    total = sum(p.numel() for p in ps)
+                    gstate["buf"] = torch.zeros(total, dtype=torch.float32, device=dev)
+                    off = 0
+                    for _, i in pspan:
+                        p = ps[i]
+                        self.state.setdefault(p, {})["momentum_buffer"] = \
+                            gstate["buf"][off:off + p.numel()].view(p.shape)
+                        off += p.numel()
+                gstate["key"] = key
+                self._launch(group, gstate, gi, sum(p.numel() for p in ps), pspan[0][0], gspan[0][0],
+                             gstate.get("buf") if use_buf else None, first, True, dev)
+            else:
+                gstate["key"] = None
+                for j, p in enumerate(ps):
+                    st = self.state.setdefault(p, {})
+                    first = use_buf and "momentum_buffer" not in st
+                    if first:
+                        st["momentum_buffer"] = torch.zeros_like(
+                            p, memory_format=torch.contiguous_format)
+                    g = p.grad.contiguous()
+                    if not p.data.is_contiguous() or p.dtype != torch.float32 or \
+                            g.dtype != torch.float32:
+                        raise TypeError("fused SGD updates contiguous fp32 parameters")
+                    self._launch(group, gstate, gi, p.numel(), p.data_ptr(), g.data_ptr(),
+                                 st.get("momentum_buffer") if use_buf else None, first, j == 0, dev)
+            self._finish_group(ps, step)
+        return loss
 
 
 class RunningLoss:

@@ -656,6 +656,77 @@ int rr_distort_random_draws(int n, int h, int w, int c, const void *workspace,
  * sync; read acc / count once per epoch */
 int rr_scalar_accumulate(const float *x, double *acc, int64_t *count, rr_stream stream);
 
+/* ---- training the VGG16 judge's classifier head (05:59-82) ----
+ * Every entry point below validates on the host before any launch (null
+ * pointer / non-positive extent: RR_EINVAL; shape outside the stated support:
+ * RR_EUNSUPPORTED), uses no floating-point atomics and is bitwise repeatable
+ * from run to run. */
+
+/* nn.Linear's weight and bias grad (loss.backward() at 05:81):
+ *   dw[o][i] = sum_n dy[n][o] * x[n][i]   (torch's [fout][fin] layout, fp32)
+ *   db[o]    = sum_n dy[n][o]             (fp32; db may be null)
+ * dy [n][fout] and x [n][fin] in `dtype`; accumulate != 0 adds to dw / db.
+ * Any n >= 1 and fout >= 1, fin % 64 == 0 (rr::linear's own constraint), else
+ * RR_EUNSUPPORTED.  dy, x and dw must be 16-byte aligned (RR_EINVAL).  One
+ * workgroup owns an output tile and the whole batch reduction: each element
+ * is written once (no split-K workspace). */
+int rr_linear_wgrad(int dtype, int n, int fin, int fout, const void *dy, const void *x, float *dw,
+                    float *db, int accumulate, rr_stream stream);
+/* nn.Linear's input grad (05:81): dx[n][i] = sum_o dy[n][o] * w[o][i], dy and
+ * w in `dtype`, dx fp32 (the accumulator, unrounded).  w is the FORWARD pack of the 1x1 GEMM (rr_pack_conv with k = 1:
+ * [fout][fin] row major), so no transposed copy of the weight is needed.
+ * mask (null, or fp32 in dx's layout): dx is zeroed where mask <= 0 -- the backward of
+ * the nn.ReLU in front of the layer (torchvision's classifier).  No weight
+ * row >= fout is read.  fin % 64 == 0; 16-byte aligned pointers. */
+int rr_linear_dgrad(int dtype, int n, int fin, int fout, const void *dy, const void *w,
+                    const float *mask, float *dx, rr_stream stream);
+/* training-mode nn.Dropout(p) (torchvision's classifier under model.train(),
+ * 05:70), fp32: element e is kept iff its Philox4x32-10 draw (key (seed,
+ * *step_dev), counter e / 4, word e % 4, 24-bit uniform u) has u >= p;
+ * y = kept ? x * fp32(1 / (1 - p)) : 0 and mask[e] = kept (bytes, for the
+ * backward).  *step_dev (device int64) advances by one per call on the stream,
+ * as rr_distort_random_u8's counter does: a HIP-graph replay draws a fresh
+ * mask with no host sync.  0 <= p < 1. */
+int rr_dropout_fwd(long long numel, float p, unsigned long long seed, long long *step_dev,
+                   const float *x, float *y, uint8_t *mask, rr_stream stream);
+/* dx = mask ? g * fp32(1 / (1 - p)) : 0 with the forward's byte mask */
+int rr_dropout_bwd(long long numel, float p, const float *g, const uint8_t *mask, float *dx,
+                   rr_stream stream);
+/* the keep mask rr_dropout_fwd draws when its counter holds `step` (tests) */
+int rr_dropout_mask(long long numel, float p, unsigned long long seed, long long step, uint8_t *out,
+                    rr_stream stream);
+/* nn.CrossEntropyLoss() (mean; 05:59, 80) on [n][k] fp32 logits and int64
+ * class indices: loss[0] = mean_r (logsumexp(row r) - row r[target r]), the
+ * log-sum-exp max-subtracted with expf / logf, the row losses summed in index
+ * order (fp64).  dlogits (null, or [n][k]) = (softmax - onehot) / n times
+ * *gscale_dev (autograd's incoming grad; null: 1).  A target outside [0, k)
+ * is never used as an index: the loss is NaN and that row's gradient is zero.
+ * k <= 1024, else RR_EUNSUPPORTED.  Workspace: rr_cross_entropy_workspace. */
+size_t rr_cross_entropy_workspace(int n, int k);
+int rr_cross_entropy(int n, int k, const float *logits, const int64_t *target, float *loss,
+                     float *dlogits, const float *gscale_dev, void *ws, size_t ws_bytes,
+                     rr_stream stream);
+/* torch.max(softmax(logits, 1), 1) (13:87-92): conf[r] = max softmax of row r,
+ * pred[r] its index, the first on ties (as rr_argmax_rows).  k <= 1024. */
+int rr_softmax_max(int n, int k, const float *logits, float *conf, int64_t *pred,
+                   rr_stream stream);
+/* torch.optim.SGD (05:60: lr 1e-3, momentum 0.9) over a flat fp32 span:
+ *   g += weight_decay * p;
+ *   momentum != 0: buf = first_step ? g : momentum * buf + (1 - dampening) * g,
+ *                  g = nesterov ? g + momentum * buf : buf;
+ *   p -= lr * g.
+ * momentum == 0 uses no buffer (buf may be null).  nesterov needs momentum > 0
+ * and dampening == 0 (RR_EINVAL otherwise, as torch raises). */
+int rr_sgd(long long count, float *param, const float *grad, float *buf, float lr, float momentum,
+           float dampening, float weight_decay, int nesterov, int first_step, rr_stream stream);
+/* capturable SGD (HIP graphs), like rr_adamw_dev: the learning rate is
+ * *lr_dev; with advance != 0 *step_dev is incremented on the stream first,
+ * and the update is the first step iff the counter then reads 1 (one counter
+ * serves all parameters of a group: advance only on the first of them). */
+int rr_sgd_dev(long long count, float *param, const float *grad, float *buf, const float *lr_dev,
+               float momentum, float dampening, float weight_decay, int nesterov,
+               int64_t *step_dev, int advance, rr_stream stream);
+
 /* async memset of a device buffer (zero_grad of the flat buffers) */
 int rr_zero(void *p, size_t bytes, rr_stream stream);
 
