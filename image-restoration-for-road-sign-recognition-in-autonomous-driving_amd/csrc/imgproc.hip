@@ -8,6 +8,9 @@
 //     22-bit fixed point, an 8-bit clip after each pass.  Optionally fused with
 //     ToTensor (x / 255 in fp32) and Normalize ((x - mean) / std in fp32, 18:31)
 //     into an NCHW fp32 batch.
+//   * rr_resize_ragged_u8: the same resample for n images of unequal size in
+//     one buffer (the reference resizes each GTSRB image on its own, 05:24-29,
+//     17:66, 18:28-32): two launches for any n, the intermediate image in LDS.
 //   * rr_cv_resize_linear_u8: cv2.resize(img, (ow, oh)) INTER_LINEAR, the
 //     clean side of the 08 PSNR leg (08:118-119) -- OpenCV's own fixed-point
 //     bilinear (resize.cpp resizeGeneric_ + HResizeLinear / VResizeLinear),
@@ -85,6 +88,43 @@ __device__ __forceinline__ int rs_clip8(int s) {          // PIL clip8: lookups[
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
+// one output sample of a pass: the rounded fixed-point sum of cnt taps of C
+// interleaved channels, src advancing by stride bytes per tap (C for the
+// horizontal pass, a row of the intermediate for the vertical one)
+template <int C, typename Stride>
+__device__ __forceinline__ void rs_tap_sum(const uint8_t *__restrict__ src, Stride stride,
+                                           const int *__restrict__ k, int cnt, int (&s)[C]) {
+#pragma unroll
+  for (int c = 0; c < C; ++c) s[c] = 1 << (RS_PREC - 1);
+  for (int x = 0; x < cnt; ++x) {
+    const int kx = k[x];
+#pragma unroll
+    for (int c = 0; c < C; ++c) s[c] += (int)src[x * stride + c] * kx;
+  }
+}
+
+struct RsNorm { float mean[4], std[4]; };
+
+// the vertical pass's store of output pixel (img, oy, ox): u8 NHWC (MODE 0) or
+// fp32 NCHW ToTensor (+ Normalize) (MODE 1)
+template <int C, int MODE>
+__device__ __forceinline__ void rs_emit(const int (&s)[C], void *__restrict__ out, int img, int oy,
+                                        int ox, int oh, int ow, const RsNorm &nm, int normalize) {
+  if constexpr (MODE == 0) {
+    uint8_t *dst = (uint8_t *)out + (((long long)img * oh + oy) * ow + ox) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) dst[c] = (uint8_t)rs_clip8(s[c]);
+  } else {
+    float *dst = (float *)out;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      float v = (float)rs_clip8(s[c]) / 255.0f;                 // ToTensor: .div(255)
+      if (normalize) v = (v - nm.mean[c]) / nm.std[c];          // Normalize: sub_, div_
+      dst[(((long long)img * C + c) * oh + oy) * ow + ox] = v;
+    }
+  }
+}
+
 // horizontal pass over source rows [y_first, y_first + rows): [n][h][w][C] ->
 // tmp [n][rows][ow][C]
 template <int C>
@@ -98,23 +138,13 @@ __global__ void rs_horiz_kernel(int n, int h, int w, int ow, int y_first, int ro
     const long long r = i / ow;                    // n * rows + row
     const int img = (int)(r / rows), y = (int)(r % rows) + y_first;
     const int xmin = bounds[2 * ox], xcnt = bounds[2 * ox + 1];
-    const int *k = kk + (long long)ox * ksize;
-    const uint8_t *src = in + (((long long)img * h + y) * w + xmin) * C;
     int s[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) s[c] = 1 << (RS_PREC - 1);
-    for (int x = 0; x < xcnt; ++x) {
-      const int kx = k[x];
-#pragma unroll
-      for (int c = 0; c < C; ++c) s[c] += (int)src[x * C + c] * kx;
-    }
+    rs_tap_sum<C>(in + (((long long)img * h + y) * w + xmin) * C, C, kk + (long long)ox * ksize, xcnt, s);
     uint8_t *dst = tmp + i * C;
 #pragma unroll
     for (int c = 0; c < C; ++c) dst[c] = (uint8_t)rs_clip8(s[c]);
   }
 }
-
-struct RsNorm { float mean[4], std[4]; };
 
 // vertical pass: tmp [n][rows][ow][C] -> u8 [n][oh][ow][C] (MODE 0) or fp32
 // NCHW ToTensor (+ Normalize) (MODE 1)
@@ -130,29 +160,10 @@ __global__ void rs_vert_kernel(int n, int rows, int oh, int ow, int ksize, int y
     const long long r = i / ow;
     const int img = (int)(r / oh), oy = (int)(r % oh);
     const int ymin = bounds[2 * oy] - y_first, ycnt = bounds[2 * oy + 1];
-    const int *k = kk + (long long)oy * ksize;
-    const uint8_t *src = tmp + (((long long)img * rows + ymin) * ow + ox) * C;
     int s[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) s[c] = 1 << (RS_PREC - 1);
-    for (int y = 0; y < ycnt; ++y) {
-      const int ky = k[y];
-#pragma unroll
-      for (int c = 0; c < C; ++c) s[c] += (int)src[(long long)y * ow * C + c] * ky;
-    }
-    if constexpr (MODE == 0) {
-      uint8_t *dst = (uint8_t *)out + i * C;
-#pragma unroll
-      for (int c = 0; c < C; ++c) dst[c] = (uint8_t)rs_clip8(s[c]);
-    } else {
-      float *dst = (float *)out;
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        float v = (float)rs_clip8(s[c]) / 255.0f;                 // ToTensor: .div(255)
-        if (normalize) v = (v - nm.mean[c]) / nm.std[c];          // Normalize: sub_, div_
-        dst[(((long long)img * C + c) * oh + oy) * ow + ox] = v;
-      }
-    }
+    rs_tap_sum<C>(tmp + (((long long)img * rows + ymin) * ow + ox) * C, (long long)ow * C,
+                  kk + (long long)oy * ksize, ycnt, s);
+    rs_emit<C, MODE>(s, out, img, oy, ox, oh, ow, nm, normalize);
   }
 }
 
@@ -230,6 +241,158 @@ static bool rs_plan(int n, int h, int w, int c, int oh, int ow, RsPlan *p) {
   p->off_tmp = o; o = al(o + (size_t)n * p->rows * ow * c);
   p->total = o;
   return true;
+}
+
+// --------------------------------------------------------- ragged resize ----
+// The same two passes for n images of unequal size lying in one byte buffer
+// (rr_resize_ragged_u8): two launches whatever n is, and no per-image work on
+// the host.
+//   1. rg_coeffs_kernel: rs_coeffs_one for every (image, axis, output index),
+//      each image's tables at a fixed stride in the workspace.  The stride is
+//      that of the largest admissible image (max_h x max_w): rs_ksize grows
+//      with the input size, and rs_coeffs_one zero-fills the taps past an
+//      image's own count.
+//   2. rg_resample_kernel: one workgroup per (image, band of output rows).
+//      It runs the horizontal pass over the source rows the band's vertical
+//      taps cover into an LDS tile [rows][ow][C] of uint8 (PIL's clipped
+//      intermediate image), then the vertical pass out of that tile: the
+//      intermediate never reaches HBM.
+// Both kernels test every table record with rg_valid before they touch the
+// image: a record outside [1, max_h] x [1, max_w] or outside the buffer reads
+// nothing and its output is zeros.
+constexpr int RG_T = 256;
+constexpr int RG_BAND_MAX = 16;            // output rows per workgroup, at most
+constexpr int RG_MIN_GROUPS = 512;         // bands shrink (down to 4 rows) to launch this many
+constexpr size_t RG_LDS_PREF = 32u << 10;  // tile bytes the band height is sized for
+constexpr size_t RG_LDS_MAX = 64u << 10;   // tile bytes a one-row band may take
+
+struct RgArgs {
+  int n, max_h, max_w, oh, ow, kh, kv, band, tile_rows;
+  long long in_bytes;
+  const uint8_t *in;
+  const rr_ragged_image *tab;
+  char *ws;
+  size_t per_image, off_bh, off_kh, off_bv, off_kv;
+};
+
+__host__ __device__ inline bool rg_valid(const rr_ragged_image &r, int c, int max_h, int max_w,
+                                         long long in_bytes) {
+  if (r.h < 1 || r.h > max_h || r.w < 1 || r.w > max_w) return false;
+  if (r.offset < 0 || r.offset > in_bytes) return false;
+  return (long long)r.h * r.w <= (in_bytes - r.offset) / c;
+}
+
+__global__ void rg_coeffs_kernel(RgArgs a, int c) {
+  const int per = a.ow + a.oh;
+  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (i >= (long long)a.n * per) return;
+  const int img = (int)(i / per), j = (int)(i % per);
+  const rr_ragged_image r = a.tab[img];
+  if (!rg_valid(r, c, a.max_h, a.max_w, a.in_bytes)) return;
+  char *base = a.ws + (size_t)img * a.per_image;
+  if (j < a.ow)
+    rs_coeffs_one(RsAxis{r.w, a.ow, a.kh, (int *)(base + a.off_bh), (int *)(base + a.off_kh)}, j);
+  else
+    rs_coeffs_one(RsAxis{r.h, a.oh, a.kv, (int *)(base + a.off_bv), (int *)(base + a.off_kv)}, j - a.ow);
+}
+
+template <int C, int MODE>
+__global__ __launch_bounds__(RG_T) void rg_resample_kernel(RgArgs a, void *__restrict__ out, RsNorm nm,
+                                                           int normalize) {
+  extern __shared__ uint8_t rg_tile[];                       // [rows][ow][C]
+  const int bands = (a.oh + a.band - 1) / a.band;
+  const int img = blockIdx.x / bands, oy0 = (blockIdx.x % bands) * a.band;
+  const int nb = a.oh - oy0 < a.band ? a.oh - oy0 : a.band;
+  const rr_ragged_image r = a.tab[img];
+  const char *base = a.ws + (size_t)img * a.per_image;
+  const int *bh = (const int *)(base + a.off_bh), *kh = (const int *)(base + a.off_kh);
+  const int *bv = (const int *)(base + a.off_bv), *kv = (const int *)(base + a.off_kv);
+  // all of this is uniform over the workgroup, so is the early return
+  bool ok = rg_valid(r, C, a.max_h, a.max_w, a.in_bytes);
+  int y0 = 0, rows = 0;
+  if (ok) {
+    const int last = oy0 + nb - 1;
+    y0 = bv[2 * oy0];
+    rows = bv[2 * last] + bv[2 * last + 1] - y0;
+    ok = y0 >= 0 && rows >= 0 && rows <= a.tile_rows && y0 + rows <= r.h;
+  }
+  if (!ok) {
+    for (int i = threadIdx.x; i < nb * a.ow; i += RG_T) {
+      const int ly = i / a.ow, ox = i - ly * a.ow, oy = oy0 + ly;
+      if constexpr (MODE == 0) {
+        uint8_t *dst = (uint8_t *)out + (((long long)img * a.oh + oy) * a.ow + ox) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) dst[c] = 0;
+      } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) ((float *)out)[(((long long)img * C + c) * a.oh + oy) * a.ow + ox] = 0.f;
+      }
+    }
+    return;
+  }
+  const uint8_t *src = a.in + r.offset + (long long)y0 * r.w * C;
+  for (int i = threadIdx.x; i < rows * a.ow; i += RG_T) {
+    const int ry = i / a.ow, ox = i - ry * a.ow;
+    const int xmin = bh[2 * ox], xcnt = bh[2 * ox + 1];
+    int s[C];
+    rs_tap_sum<C>(src + ((long long)ry * r.w + xmin) * C, C, kh + (long long)ox * a.kh, xcnt, s);
+#pragma unroll
+    for (int c = 0; c < C; ++c) rg_tile[i * C + c] = (uint8_t)rs_clip8(s[c]);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nb * a.ow; i += RG_T) {
+    const int ly = i / a.ow, ox = i - ly * a.ow, oy = oy0 + ly;
+    const int ymin = bv[2 * oy] - y0, ycnt = bv[2 * oy + 1];
+    int s[C];
+    rs_tap_sum<C>(rg_tile + (ymin * a.ow + ox) * C, a.ow * C, kv + (long long)oy * a.kv, ycnt, s);
+    rs_emit<C, MODE>(s, out, img, oy, ox, a.oh, a.ow, nm, normalize);
+  }
+}
+
+struct RgPlan {
+  int kh, kv, band, tile_rows;
+  size_t lds, per_image, off_bh, off_kh, off_bv, off_kv, total;
+};
+
+// source rows a band of `band` output rows can cover, for any image up to
+// max_h rows: last tap - first tap <= (band - 1) * scale + 2 * support + 1
+// (rs_coeffs_one's xmin / xmax, one truncation each way), and both scale and
+// support grow with the image's height
+static long long rg_tile_rows(int max_h, int oh, int band) {
+  const double scale = (double)max_h / oh;
+  const double support = scale < 1.0 ? 1.0 : scale;
+  const long long rows = (long long)((band - 1) * scale + 2.0 * support + 1.0) + 1;
+  return rows < max_h ? rows : max_h;
+}
+
+// RR_OK, RR_EINVAL (arguments) or RR_EUNSUPPORTED (more than RS_MAXK taps, or
+// a one-row band's tile larger than RG_LDS_MAX)
+static int rg_plan(int n, int c, int max_h, int max_w, int oh, int ow, RgPlan *p) {
+  if (n <= 0 || max_h <= 0 || max_w <= 0 || oh <= 0 || ow <= 0 || c < 1 || c > 4) return RR_EINVAL;
+  // rs_ksize's ceil(scale) * 2 + 1 <= RS_MAXK, without its int overflowing
+  if ((max_w - 1) / ow >= RS_MAXK / 2 || (max_h - 1) / oh >= RS_MAXK / 2) return RR_EUNSUPPORTED;
+  p->kh = rs_ksize(max_w, ow);
+  p->kv = rs_ksize(max_h, oh);
+  if (p->kh > RS_MAXK || p->kv > RS_MAXK) return RR_EUNSUPPORTED;
+  if ((long long)n * ((long long)oh + ow) > (1LL << 31)) return RR_EUNSUPPORTED;   // grid sizes
+  auto tile = [&](int band) { return (size_t)rg_tile_rows(max_h, oh, band) * ow * c; };
+  if ((size_t)ow * c > RG_LDS_MAX) return RR_EUNSUPPORTED;
+  int band = oh < RG_BAND_MAX ? oh : RG_BAND_MAX;
+  while (band > 1 && tile(band) > RG_LDS_PREF) --band;
+  if (tile(band) > RG_LDS_MAX) return RR_EUNSUPPORTED;
+  while (band > 4 && (long long)n * ((oh + band - 1) / band) < RG_MIN_GROUPS) band = (band + 1) / 2;
+  p->band = band;
+  p->tile_rows = (int)rg_tile_rows(max_h, oh, band);
+  p->lds = tile(band);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t o = 0;
+  p->off_bh = o; o = al(o + (size_t)ow * 2 * 4);
+  p->off_kh = o; o = al(o + (size_t)ow * p->kh * 4);
+  p->off_bv = o; o = al(o + (size_t)oh * 2 * 4);
+  p->off_kv = o; o = al(o + (size_t)oh * p->kv * 4);
+  p->per_image = o;
+  p->total = o * (size_t)n;
+  return RR_OK;
 }
 
 // ------------------------------------------------------------------ SSIM ----
@@ -425,6 +588,60 @@ extern "C" int rr_resize_bilinear_u8(int n, int h, int w, int c, int oh, int ow,
     default: RS_LAUNCH(4) break;
   }
 #undef RS_LAUNCH
+  RR_CHECK_LAUNCH();
+  return RR_OK;
+}
+
+extern "C" int rr_ragged_check(int n, int c, size_t in_bytes, const rr_ragged_image *images_host,
+                               int max_h, int max_w, int oh, int ow) {
+  if (!images_host || n <= 0 || max_h <= 0 || max_w <= 0 || oh <= 0 || ow <= 0 || c < 1 || c > 4)
+    return RR_EINVAL;
+  if ((max_w - 1) / ow >= RS_MAXK / 2 || (max_h - 1) / oh >= RS_MAXK / 2) return RR_EUNSUPPORTED;
+  if (in_bytes > (size_t)INT64_MAX) return RR_EINVAL;
+  for (int i = 0; i < n; ++i)
+    if (!rg_valid(images_host[i], c, max_h, max_w, (long long)in_bytes)) return RR_EINVAL;
+  return RR_OK;
+}
+
+extern "C" size_t rr_resize_ragged_workspace(int n, int c, int max_h, int max_w, int oh, int ow) {
+  RgPlan p;
+  return rg_plan(n, c, max_h, max_w, oh, ow, &p) == RR_OK ? p.total : 0;
+}
+
+extern "C" int rr_resize_ragged_u8(int n, int c, int max_h, int max_w, int oh, int ow,
+                                   const uint8_t *in, size_t in_bytes,
+                                   const rr_ragged_image *images_dev, int out_kind, const float *mean,
+                                   const float *std, void *out, void *ws, size_t ws_bytes,
+                                   rr_stream stream) {
+  RgPlan p;
+  if (!in || !images_dev || !out || !ws || (out_kind != 0 && out_kind != 1)) return RR_EINVAL;
+  if (in_bytes == 0 || in_bytes > (size_t)INT64_MAX) return RR_EINVAL;
+  if (const int rc = rg_plan(n, c, max_h, max_w, oh, ow, &p)) return rc;
+  if (ws_bytes < p.total) return RR_EWORKSPACE;
+  if ((mean == nullptr) != (std == nullptr) || (mean && out_kind != 1)) return RR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const RgArgs a{n, max_h, max_w, oh, ow, p.kh, p.kv, p.band, p.tile_rows, (long long)in_bytes,
+                 in, images_dev, (char *)ws, p.per_image, p.off_bh, p.off_kh, p.off_bv, p.off_kv};
+  const long long nco = (long long)n * (ow + oh);
+  hipLaunchKernelGGL(rg_coeffs_kernel, dim3((unsigned)((nco + 63) / 64)), dim3(64), 0, st, a, c);
+  RR_CHECK_LAUNCH();
+  RsNorm nm{};
+  for (int i = 0; i < c; ++i) {
+    nm.mean[i] = mean ? mean[i] : 0.f;
+    nm.std[i] = std ? std[i] : 1.f;
+  }
+  const int norm = mean != nullptr;
+  const dim3 g((unsigned)((long long)n * ((oh + p.band - 1) / p.band))), b(RG_T);
+#define RG_LAUNCH(CC)                                                                              \
+  if (out_kind == 0) hipLaunchKernelGGL((rg_resample_kernel<CC, 0>), g, b, p.lds, st, a, out, nm, norm); \
+  else hipLaunchKernelGGL((rg_resample_kernel<CC, 1>), g, b, p.lds, st, a, out, nm, norm);
+  switch (c) {
+    case 1: RG_LAUNCH(1) break;
+    case 2: RG_LAUNCH(2) break;
+    case 3: RG_LAUNCH(3) break;
+    default: RG_LAUNCH(4) break;
+  }
+#undef RG_LAUNCH
   RR_CHECK_LAUNCH();
   return RR_OK;
 }

@@ -66,6 +66,10 @@ class DistortParam(C.Structure):
                 ("flags", C.c_int32), ("ksize", C.c_int32)]
 
 
+class RaggedImage(C.Structure):             # mirrors rr_ragged_image
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 class BnFinalizeDesc(C.Structure):          # mirrors rr_bn_finalize_desc
     _fields_ = [("C", C.c_int32), ("blocks", C.c_int32), ("count", C.c_int64),
                 ("part", C.c_void_p), ("bias", C.c_void_p), ("gamma", C.c_void_p),
@@ -179,6 +183,9 @@ _SIGS = {
     "rr_resize_workspace": (S_, [I_, I_, I_, I_, I_, I_]),
     "rr_cv_resize_linear_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, P_, I_, P_]),
     "rr_resize_bilinear_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, I_, P_, P_, P_, P_, S_, P_]),
+    "rr_ragged_check": (I_, [I_, I_, S_, P_, I_, I_, I_, I_]),
+    "rr_resize_ragged_workspace": (S_, [I_, I_, I_, I_, I_, I_]),
+    "rr_resize_ragged_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, S_, P_, I_, P_, P_, P_, P_, S_, P_]),
     "rr_ssim_workspace": (S_, [I_, I_]),
     "rr_ssim_u8": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, S_, P_]),
     "rr_distort_workspace": (S_, [I_, I_, I_, I_]),

@@ -17,23 +17,32 @@ DataLoader workers and in the inference loop).  Here they take a whole
 * ``cv_resize`` -- ``cv2.resize(img, (224, 224))`` of the 08 PSNR leg's
   clean image (08:118-119): OpenCV's INTER_LINEAR, which is not PIL's.
 * ``psnr`` / ``ssim`` -- 08:123-125 (skimage semantics, data_range 255).
+* ``RaggedBatch`` / ``read_ppm`` / ``ImageFolder`` / ``find_images`` -- the
+  step before the first tensor: GTSRB's ``.ppm`` files have unequal sizes and
+  the reference resizes each on its own (05:24-32, 14:68, 18:28-36).  A
+  ``RaggedBatch`` holds n images of unequal size in one device buffer;
+  ``Resize`` / ``Compose`` turn it into the dense batch in two launches.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 import random as _random
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
 
+import numpy as np
 import torch
 
 from . import ops
 from ._lib import (RR_DISTORT_BLUR, RR_DISTORT_FOG, RR_DISTORT_KMAX, RR_DISTORT_NOISE,
-                   DistortParam, lib)
+                   DistortParam, RaggedImage, lib)
 
 __all__ = ["Resize", "ToTensor", "Normalize", "Compose", "apply_random_distortions",
            "encode_png", "write_png",
            "RandomDistortion", "motion_blur_table",
            "apply_compound_distortion", "distortion_params", "psnr", "ssim", "cv_resize",
+           "RaggedBatch", "read_ppm", "ImageFolder", "find_images",
            "IMAGENET_MEAN", "IMAGENET_STD"]
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)      # 18:31
@@ -59,6 +68,8 @@ class Resize:
         self.size = (int(size[0]), int(size[1]))
 
     def __call__(self, x):
+        if isinstance(x, RaggedBatch):
+            return x.resize(self.size[0], self.size[1], out="u8")
         _check_u8(x)
         return ops.resize_bilinear_u8(x, self.size[0], self.size[1], out="u8")
 
@@ -67,6 +78,9 @@ class ToTensor:
     """u8 [n, h, w, c] -> fp32 [n, c, h, w] / 255."""
 
     def __call__(self, x):
+        if isinstance(x, RaggedBatch):
+            raise TypeError("ToTensor needs a dense batch: a RaggedBatch has no common shape "
+                            "(put Resize first)")
         _check_u8(x)
         n, h, w, c = x.shape
         return ops.resize_bilinear_u8(x, h, w, out="f32")
@@ -88,7 +102,8 @@ class Normalize:
 
 class Compose:
     """Sequential transforms; ``[Resize, ToTensor]`` and ``[Resize, ToTensor,
-    Normalize]`` prefixes fuse into one resample pass writing fp32 NCHW."""
+    Normalize]`` prefixes fuse into one resample pass writing fp32 NCHW, for
+    a dense batch and for a ``RaggedBatch`` alike."""
 
     def __init__(self, transforms):
         self.transforms = list(transforms)
@@ -102,11 +117,256 @@ class Compose:
             if len(t) >= 3 and isinstance(t[2], Normalize):
                 mean, std = t[2].mean, t[2].std
                 i = 3
-            _check_u8(x)
-            x = ops.resize_bilinear_u8(x, t[0].size[0], t[0].size[1], out="f32", mean=mean, std=std)
+            if isinstance(x, RaggedBatch):
+                x = x.resize(t[0].size[0], t[0].size[1], out="f32", mean=mean, std=std)
+            else:
+                _check_u8(x)
+                x = ops.resize_bilinear_u8(x, t[0].size[0], t[0].size[1], out="f32", mean=mean, std=std)
         for tr in t[i:]:
             x = tr(x)
         return x
+
+
+# ---------------------------------------------------------------------------
+# ragged batches: files of unequal size -> the first tensor
+
+_RECORD = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4")])     # rr_ragged_image
+assert _RECORD.itemsize == C.sizeof(RaggedImage) == 16
+
+
+def _host_buffer(nbytes, device):
+    """uint8 host staging buffer, pinned when it feeds a device copy"""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8,
+                       pin_memory=torch.device(device).type == "cuda")
+
+
+class RaggedBatch:
+    """n HWC uint8 images of unequal size in one buffer.
+
+    ``data``: 1-D uint8 tensor; ``table``: [n, 16] uint8 tensor on the same
+    device, n ``rr_ragged_image`` records (byte offset, h, w); ``sizes``: the
+    host list of (h, w); ``channels``; ``max_hw``: the bound the device code
+    holds every record to (the batch's own maximum unless given -- give it to
+    keep one captured graph valid across batches).  ``records`` is a numpy
+    array of the records or a sequence of (offset, h, w).
+
+    The constructor runs ``rr_ragged_check`` on the host records against the
+    buffer's size and raises ``ValueError`` if any image leaves it: nothing is
+    launched.  ``Resize`` / ``Compose`` accept a RaggedBatch in place of the
+    dense [n, h, w, c] tensor."""
+
+    def __init__(self, data, records, channels=3, max_hw=None):
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1:
+            raise TypeError("RaggedBatch data: expected a 1-D uint8 tensor")
+        rec = np.ascontiguousarray(np.asarray(records, dtype=_RECORD).reshape(-1))
+        n = rec.shape[0]
+        if n == 0:
+            raise ValueError("RaggedBatch: no images")
+        if max_hw is None:
+            max_hw = (max(int(rec["h"].max()), 1), max(int(rec["w"].max()), 1))
+        max_hw = (int(max_hw[0]), int(max_hw[1]))
+        rc = lib().rr_ragged_check(n, int(channels), data.numel(), rec.ctypes.data,
+                                   max_hw[0], max_hw[1], max_hw[0], max_hw[1])
+        if rc != 0:
+            c = int(channels)
+            bad = [i for i in range(n)
+                   if not (1 <= rec["h"][i] <= max_hw[0] and 1 <= rec["w"][i] <= max_hw[1]
+                           and 0 <= rec["offset"][i]
+                           and int(rec["offset"][i]) + int(rec["h"][i]) * int(rec["w"][i]) * c <= data.numel())]
+            where = f"image {bad[0]}: offset {int(rec['offset'][bad[0]])}, " \
+                    f"{int(rec['h'][bad[0]])} x {int(rec['w'][bad[0]])}" if bad else f"channels {c}"
+            raise ValueError(f"RaggedBatch: table rejected by rr_ragged_check ({rc}): {where}; "
+                             f"buffer {data.numel()} bytes, bound {max_hw}")
+        self.data = data.contiguous()
+        self.records = rec
+        self.channels = int(channels)
+        self.max_hw = max_hw
+        self.sizes = [(int(h), int(w)) for h, w in zip(rec["h"], rec["w"])]
+        host = torch.from_numpy(rec.view(np.uint8).reshape(n, 16).copy())
+        if data.is_cuda:
+            host = host.pin_memory()
+        self.table = host.to(data.device, non_blocking=True)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def to(self, device, non_blocking=False):
+        """the batch on ``device``: one copy of the buffer, one of the table"""
+        return RaggedBatch(self.data.to(device, non_blocking=non_blocking), self.records,
+                           self.channels, self.max_hw)
+
+    @classmethod
+    def from_arrays(cls, images, device):
+        """A list of [h, w, c] (or [h, w]) uint8 numpy arrays / torch tensors
+        of unequal sizes -> RaggedBatch on ``device``: the images are packed
+        back to back into one host buffer and copied in one H2D copy."""
+        arrs = []
+        for im in images:
+            a = im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+            if a.dtype != np.uint8 or a.ndim not in (2, 3):
+                raise TypeError("RaggedBatch.from_arrays: expected [h, w, c] uint8 images")
+            arrs.append(a[:, :, None] if a.ndim == 2 else a)
+        if not arrs:
+            raise ValueError("RaggedBatch: no images")
+        c = arrs[0].shape[2]
+        if any(a.shape[2] != c for a in arrs):
+            raise ValueError("RaggedBatch.from_arrays: images differ in channel count")
+        rec = np.zeros(len(arrs), dtype=_RECORD)
+        rec["h"] = [a.shape[0] for a in arrs]
+        rec["w"] = [a.shape[1] for a in arrs]
+        nbytes = np.array([a.size for a in arrs], dtype=np.int64)
+        rec["offset"] = np.cumsum(nbytes) - nbytes
+        host = _host_buffer(nbytes.sum(), device)
+        buf = host.numpy()
+        for a, o, nb in zip(arrs, rec["offset"], nbytes):
+            buf[o:o + nb] = a.reshape(-1)
+        return cls(host[:max(int(nbytes.sum()), 1)].to(device, non_blocking=True), rec, c)
+
+    def resize(self, oh, ow, out="u8", mean=None, std=None):
+        """every image through PIL's bilinear resample to (oh, ow): the dense
+        [n, oh, ow, c] uint8 or [n, c, oh, ow] fp32 batch (ops.resize_ragged_u8)"""
+        if mean is not None and (len(mean) != self.channels or len(std) != self.channels):
+            raise ValueError(f"Normalize: {len(mean)} means for {self.channels} channels")
+        return ops.resize_ragged_u8(self.data, self.table, self.max_hw, self.channels, oh, ow,
+                                    out=out, mean=mean, std=std)
+
+
+_PPM_WS = b" \t\n\r\x0b\x0c"
+_PPM_HEAD = 1 << 16            # a header (comments included) is searched this far
+
+
+def _ppm_header(head, path):
+    """The first bytes of a binary PPM -> (w, h, maxval, payload offset).
+    Netpbm's grammar: the magic "P6", then width, height and maxval in decimal,
+    separated by any whitespace, with "#" comments running to the end of their
+    line; exactly ONE whitespace byte after maxval, and the pixels follow (they
+    may themselves look like whitespace or digits)."""
+    if head[:2] != b"P6":
+        raise ValueError(f"{path}: not a binary PPM (magic {bytes(head[:2])!r}, expected b'P6')")
+    n, pos, vals = len(head), 2, []
+    if n < 3 or not (head[2] in _PPM_WS or head[2] == 0x23):
+        raise ValueError(f"{path}: malformed PPM header")
+    for _ in range(3):
+        while pos < n and (head[pos] in _PPM_WS or head[pos] == 0x23):
+            if head[pos] == 0x23:
+                while pos < n and head[pos] not in b"\r\n":
+                    pos += 1
+            else:
+                pos += 1
+        start = pos
+        while pos < n and 0x30 <= head[pos] <= 0x39:
+            pos += 1
+        if pos == start:
+            raise ValueError(f"{path}: malformed PPM header")
+        vals.append(int(head[start:pos]))
+    if pos >= n or head[pos] not in _PPM_WS:
+        raise ValueError(f"{path}: malformed PPM header (no whitespace after maxval)")
+    return vals[0], vals[1], vals[2], pos + 1
+
+
+def read_ppm(paths, device, threads=0):
+    """Binary PPM files (P6, maxval <= 255: what GTSRB ships) -> RaggedBatch on
+    ``device``.  The whole files are read by a thread pool into one host
+    buffer (pinned for a GPU), their headers parsed on the host, and the table
+    offsets point just past each header: the decode IS the offset.  One
+    non-blocking H2D copy moves all of it.  ``threads``: pool size, 0 = up to
+    8.  Any other file (P3, P5, 16-bit, truncated) raises ``ValueError`` naming
+    it.  Samples are taken as stored (GTSRB's maxval is 255; a smaller maxval
+    is not rescaled).  With ``device="cpu"`` the batch stays on the host
+    (``.to(device)`` later)."""
+    paths = [os.fspath(p) for p in paths]
+    n = len(paths)
+    if n == 0:
+        raise ValueError("read_ppm: no paths")
+    fsize = np.array([os.path.getsize(p) for p in paths], dtype=np.int64)
+    start = np.cumsum(fsize) - fsize
+    total = int(fsize.sum())
+    host = _host_buffer(total, device)
+    buf = host.numpy()
+    rec = np.zeros(n, dtype=_RECORD)
+
+    def one(i):
+        a, b = int(start[i]), int(start[i] + fsize[i])
+        with open(paths[i], "rb") as f:
+            got = f.readinto(memoryview(buf[a:b])) if b > a else 0
+        w, h, maxval, off = _ppm_header(bytes(buf[a:a + min(got, _PPM_HEAD)]), paths[i])
+        if not 1 <= maxval <= 255:
+            raise ValueError(f"{paths[i]}: maxval {maxval}: only 8-bit PPM (maxval <= 255) is read")
+        if h < 1 or w < 1 or h > 2 ** 31 - 1 or w > 2 ** 31 - 1:
+            raise ValueError(f"{paths[i]}: bad PPM size {w} x {h}")
+        if off + h * w * 3 > got:
+            raise ValueError(f"{paths[i]}: truncated PPM: {w} x {h} needs {h * w * 3} pixel bytes, "
+                             f"{max(got - off, 0)} present")
+        rec[i] = (a + off, h, w)
+
+    workers = int(threads) if threads else min(8, n)
+    if workers <= 1:
+        for i in range(n):
+            one(i)
+    else:
+        with ThreadPoolExecutor(workers) as pool:
+            list(pool.map(one, range(n)))
+    return RaggedBatch(host[:max(total, 1)].to(device, non_blocking=True), rec, 3)
+
+
+def find_images(root, pattern="*/*.ppm"):
+    """``sorted(Path(root).glob(pattern))``: the file list of 14:68"""
+    return sorted(Path(root).glob(pattern))
+
+
+class ImageFolder:
+    """torchvision ``ImageFolder``'s view of a directory tree (05:32, 18:35),
+    read straight into device batches.  ``classes``: the sorted sub-directory
+    names of ``root``; ``class_to_idx``; ``samples``: (path, class index) in
+    class order and, within a class, in ``sorted(os.walk(dir))`` order with
+    each directory's file names sorted; the extension match ignores case.  A
+    class without files keeps its index (torchvision's ``find_classes`` counts
+    it too) and contributes no samples.
+
+    ``load(indices, device)`` -> (RaggedBatch, int64 labels on ``device``);
+    ``batches(batch_size, shuffle, generator)`` yields that for one pass over
+    the samples, the last batch short (``DataLoader(drop_last=False)``).
+    ``device`` defaults to the GPU when there is one."""
+
+    def __init__(self, root, extensions=(".ppm",), device=None, threads=0):
+        self.root = os.fspath(root)
+        self.extensions = tuple(e.lower() for e in extensions)
+        self.device = torch.device(device if device is not None
+                                   else ("cuda" if torch.cuda.is_available() else "cpu"))
+        self.threads = threads
+        self.classes = sorted(e.name for e in os.scandir(self.root) if e.is_dir())
+        if not self.classes:
+            raise FileNotFoundError(f"Couldn't find any class folder in {self.root}.")
+        self.class_to_idx = {c: i for i, c in enumerate(self.classes)}
+        self.samples = []
+        for c in self.classes:
+            for d, _, names in sorted(os.walk(os.path.join(self.root, c), followlinks=True)):
+                for name in sorted(names):
+                    if name.lower().endswith(self.extensions):
+                        self.samples.append((os.path.join(d, name), self.class_to_idx[c]))
+        self.targets = [t for _, t in self.samples]
+
+    def __len__(self):
+        return len(self.samples)
+
+    def load(self, indices, device=None):
+        device = self.device if device is None else torch.device(device)
+        indices = [int(i) for i in indices]
+        batch = read_ppm([self.samples[i][0] for i in indices], device, self.threads)
+        labels = torch.tensor([self.samples[i][1] for i in indices], dtype=torch.int64)
+        if device.type == "cuda":
+            labels = labels.pin_memory()
+        return batch, labels.to(device, non_blocking=True)
+
+    def batches(self, batch_size, shuffle=False, generator=None, device=None):
+        n = len(self.samples)
+        order = torch.randperm(n, generator=generator).tolist() if shuffle else list(range(n))
+        for a in range(0, n, int(batch_size)):
+            yield self.load(order[a:a + int(batch_size)], device)
 
 
 def distortion_params(n, rng=None):

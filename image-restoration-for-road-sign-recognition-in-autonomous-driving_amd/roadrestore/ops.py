@@ -25,6 +25,7 @@ __all__ = [
     "motion_blur_kernel", "first_conv_wgrad_act", "affine_act_pool", "nearest_resize",
     "nearest_resize_bwd", "fold_conv_bn", "bn_stats", "linear_wgrad", "linear_dgrad",
     "dropout_fwd", "dropout_bwd", "dropout_mask", "cross_entropy", "softmax_max", "sgd_",
+    "resize_ragged_u8",
 ]
 
 
@@ -1091,6 +1092,44 @@ def resize_bilinear_u8(x, oh, ow, out="u8", mean=None, std=None):
                                     C.cast(mp, C.c_void_p) if mp is not None else None,
                                     C.cast(sp, C.c_void_p) if sp is not None else None,
                                     _p(y), _p(ws), wsb, stream()), "rr_resize_bilinear_u8")
+    return y
+
+
+def resize_ragged_u8(data, table, max_hw, c, oh, ow, out="u8", mean=None, std=None):
+    """PIL-exact bilinear resize of n images of unequal size to one dense
+    batch (each image through torchvision Resize((oh, ow)) on its own, 05:24-29
+    / 17:66 / 18:28-32) in two launches.  ``data``: 1-D uint8 device buffer
+    holding the HWC images; ``table``: device [n, 16] uint8, n rr_ragged_image
+    records (imgproc.RaggedBatch builds and checks both); ``max_hw``: (max_h,
+    max_w) bounding every image.  out="u8": [n, oh, ow, c] uint8; out="f32":
+    [n, c, oh, ow] fp32 ToTensor (+ Normalize(mean, std)).  A record that fails
+    rr_ragged_check yields zeros, never an out-of-bounds read."""
+    _need_cuda(data, table)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise TypeError("resize_ragged_u8 expects a contiguous 1-D uint8 buffer")
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous():
+        raise TypeError("resize_ragged_u8 expects an [n, 16] uint8 table of rr_ragged_image records")
+    n, c = int(table.shape[0]), int(c)
+    max_h, max_w = int(max_hw[0]), int(max_hw[1])
+    oh, ow = int(oh), int(ow)
+    if out not in ("u8", "f32"):
+        raise ValueError(out)
+    kind = 0 if out == "u8" else 1
+    L = lib()
+    wsb = L.rr_resize_ragged_workspace(n, c, max_h, max_w, oh, ow)
+    if wsb == 0:
+        raise RuntimeError(f"rr_resize_ragged_u8: unsupported batch n={n} c={c} max={max_h, max_w} -> {(oh, ow)}")
+    y = torch.empty((n, oh, ow, c) if kind == 0 else (n, c, oh, ow),
+                    dtype=torch.uint8 if kind == 0 else torch.float32, device=data.device)
+    ws = _ws(wsb, data.device)
+    mp = sp = None
+    if mean is not None:
+        mp = (C.c_float * c)(*[float(v) for v in mean])
+        sp = (C.c_float * c)(*[float(v) for v in std])
+    L.check(L.rr_resize_ragged_u8(n, c, max_h, max_w, oh, ow, _p(data), data.numel(), _p(table), kind,
+                                  C.cast(mp, C.c_void_p) if mp is not None else None,
+                                  C.cast(sp, C.c_void_p) if sp is not None else None,
+                                  _p(y), _p(ws), wsb, stream()), "rr_resize_ragged_u8")
     return y
 
 

@@ -583,6 +583,34 @@ int rr_resize_bilinear_u8(int n, int h, int w, int c, int oh, int ow,
                           const float *std, void *out, void *workspace,
                           size_t workspace_bytes, rr_stream stream);
 
+/* The same resample for a ragged batch: the reference resizes every GTSRB
+ * image on its own before anything is stacked (05_train_baseline.py:24-29,
+ * 17_run_unified_inference.py:66, 18_test_unified_benchmark.py:28-32), so the
+ * n images (c channels each, 1..4, HWC uint8) have their own h x w and lie
+ * anywhere in one byte buffer `in` of in_bytes bytes; images_dev[i] (device
+ * memory) gives image i's byte offset and size.  Every image is resampled to
+ * oh x ow into the dense batch of rr_resize_bilinear_u8 (same out_kind, mean,
+ * std).  max_h / max_w bound every image's size and set the workspace layout.
+ * Two launches whatever n is, no per-image host work, graph-capturable: the
+ * table is read on the device only.  A record outside [1, max_h] x [1, max_w]
+ * or whose h * w * c bytes leave [0, in_bytes) is not read and its output is
+ * zeros; rr_ragged_check is the host-side test of a table (no launch):
+ * RR_EINVAL for such a record or bad arguments, RR_EUNSUPPORTED for more than
+ * 255 filter taps (max / out > 127).  rr_resize_ragged_u8 also returns
+ * RR_EUNSUPPORTED (and the workspace query 0) when the source rows of a
+ * single output row, ow * c bytes each, exceed the 64 KiB on-chip tile. */
+typedef struct rr_ragged_image {
+  int64_t offset;     /* byte offset of the image's first pixel in `in`      */
+  int32_t h, w;       /* its size                                            */
+} rr_ragged_image;    /* 16 bytes */
+int rr_ragged_check(int n, int c, size_t in_bytes, const rr_ragged_image *images_host,
+                    int max_h, int max_w, int oh, int ow);
+size_t rr_resize_ragged_workspace(int n, int c, int max_h, int max_w, int oh, int ow);
+int rr_resize_ragged_u8(int n, int c, int max_h, int max_w, int oh, int ow,
+                        const uint8_t *in, size_t in_bytes, const rr_ragged_image *images_dev,
+                        int out_kind, const float *mean, const float *std, void *out,
+                        void *workspace, size_t workspace_bytes, rr_stream stream);
+
 /* cv2.resize(img, (ow, oh)) with the default INTER_LINEAR, the clean image of
  * the 08 PSNR leg (08_run_inference.py:118-119): OpenCV's fixed-point
  * bilinear (resize.cpp resizeGeneric_, HResizeLinear / VResizeLinear; 11-bit
