@@ -1,0 +1,291 @@
+"""Per-element error bounds and guard bands for the kernel parity tests.
+
+A relative L2 norm over a whole tensor hides an error confined to a tile
+corner, the last column of a strip, a partial band or one image of a pair
+(tests/test_parity_cpu.py shows two such broken kernels passing 4e-3).  The
+helpers here bound every output element on its own, and wrap every operand in
+poisoned bands so that a store or a used load outside a tensor, or an element
+never written, shows up.  New kernel tests use these, not a norm.
+
+The bound (derived, not measured).  Let
+
+  u = 2^-24      unit roundoff of fp32 (24-bit significand, round to nearest);
+  K              the number of terms summed into one output: 9 cin (3x3),
+                 cin (1x1, convT up), 4 cin (convT down), n h w (a weight
+                 grad), plus 1 per added operand (bias, the accumulated y0, a
+                 residual);
+  A              the same operation on |x| and |w| (plus |bias|, |y0|, |res|):
+                 the sum of the magnitudes of the K terms.
+
+Operands are bf16-exact (their products are then exact in fp32) or fp32 (one
+rounding, u, per product).  A sum of K fp32 terms in ANY order, by FMA chain
+or by tree, has error at most (K - 1) u A + O(u^2) (Higham, Accuracy and
+Stability of Numerical Algorithms, section 4.2); with fp32 products at most
+K u A + O(u^2).  Hence, with a factor that absorbs the O(u^2) terms, the one
+extra fp32 product of a PReLU slope and the second-order term of the store
+below,
+
+  fp32 output:  bound = 2 K u A
+  bf16 output:  bound = 2^-8 |ref| + 2 K u A
+
+bf16 keeps 8 significand bits, so a store rounded once to nearest moves a
+value v by at most 2^-8 |v| (half an ulp); v is within K u A of ref, and
+2^-8 K u A is far inside the K u A the factor 2 leaves over.  An output that
+was rounded to bf16 TWICE (an intermediate stored and read back) gets
+``rounds=2``: 2 * 2^-8 |ref|; the call site must say why.
+
+ReLU, PReLU with |alpha| <= 1, and a mask taken from a separate tensor are
+1-Lipschitz: |f(a) - f(b)| <= |a - b|, so they map ref and keep the bound.
+The 2x2 max is 1-Lipschitz in the maximum norm: the pooled bound is the
+maximum of the bound over the window.
+
+BN statistics partials (summed over their rows; of the pre-bias sum): with
+e_p = 2 K u A_p the bound of pixel p and P pixels per channel summed in fp32
+in any order (error at most P u sum|t|, doubled as above),
+
+  sum:             sum_p e_p + 2 P u sum_p |ref_p|
+  sum of squares:  sum_p (2 |ref_p| e_p + e_p^2) + 2 P u sum_p ref_p^2
+
+((r + d)^2 - r^2 = 2 r d + d^2 with |d| <= e_p).
+
+References are fp64 on the CPU.  Activations are taken NCHW (torch's layout)
+and everything returned is NHWC, the kernels' layout.
+
+Plain helper module, imported like rrpath: no fixtures, no pytest settings.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+U = 2.0 ** -24          # fp32 unit roundoff
+HALF_ULP_BF16 = 2.0 ** -8   # bf16 unit roundoff (8 significand bits)
+SENTINEL = -768.0       # finite, exact in bf16 and fp32
+
+
+# ---------------------------------------------------------------------------
+# the check
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def assert_within(got, ref64, bound64, what, nchw=False):
+    """|got - ref64| <= bound64 for every element; a NaN in ``got`` is a
+    violation.  ``got`` in the layout of ``ref64`` (NHWC), or NCHW with
+    ``nchw`` (the fp32 model-boundary outputs).  The failure message gives the
+    number of violations, the worst ratio and the NHWC index of the worst
+    element with its position in the 8 / 16-row and 16 / 32-column grids the
+    kernels tile by."""
+    got = got.detach().double().cpu()
+    if nchw:
+        got = _nhwc(got)
+    assert got.shape == ref64.shape == bound64.shape, (what, got.shape, ref64.shape, bound64.shape)
+    assert bool((bound64 >= 0).all()) and bool(torch.isfinite(ref64).all()), what
+    err = (got - ref64).abs()
+    bad = ~(err <= bound64)                       # NaN compares false: a violation
+    count = int(bad.sum())
+    if count == 0:
+        return
+    ratio = err / bound64.clamp_min(1e-300)
+    ratio = torch.where(torch.isnan(got), torch.full_like(ratio, math.inf), ratio)
+    flat = int(torch.where(bad, ratio, torch.full_like(ratio, -1.0)).argmax())
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(flat), got.shape))
+    where = ""
+    if got.dim() == 4:
+        _, h, w, _ = idx
+        where = (f" [n, h, w, c] of {tuple(got.shape)}: row {h} = {h // 16}*16+{h % 16} = {h // 8}*8+{h % 8},"
+                 f" column {w} = {w // 32}*32+{w % 32} = {w // 16}*16+{w % 16}, channel {idx[3]}"
+                 f" = {idx[3] // 32}*32+{idx[3] % 32};")
+    first = [tuple(int(i) for i in r) for r in bad.nonzero()[:6]]
+    raise AssertionError(
+        f"{what}: {count} of {got.numel()} elements outside the bound ({int(torch.isnan(got).sum())} NaN);"
+        f" worst ratio {float(ratio.reshape(-1)[flat]):.3g} at {idx}{where}"
+        f" got {float(got.reshape(-1)[flat])!r}, ref {float(ref64.reshape(-1)[flat])!r},"
+        f" bound {float(bound64.reshape(-1)[flat]):.3g}; first violations {first}")
+
+
+def worst_ratio(got, ref64, bound64):
+    """max |got - ref| / bound (for printing how much of a bound is used)"""
+    got = got.detach().double().cpu()
+    return float(((got - ref64).abs() / bound64.clamp_min(1e-300)).max())
+
+
+# ---------------------------------------------------------------------------
+# bounds
+
+def _round_term(ref, out_dtype, rounds):
+    if out_dtype == torch.float32:
+        assert rounds == 1
+        return torch.zeros_like(ref)
+    assert out_dtype == torch.bfloat16 and rounds in (1, 2)
+    return rounds * HALF_ULP_BF16 * ref.abs()
+
+
+def _finish(ref, A, K, out_dtype, rounds):
+    return ref, _round_term(ref, out_dtype, rounds) + 2.0 * K * U * A
+
+
+def conv_terms(x, w, padding):
+    """(ref, A) of the plain convolution, fp64 NHWC: the sum and the sum of
+    the magnitudes of its terms (shared by the epilogue variants of a shape)."""
+    x, w = x.double(), w.double()
+    return _nhwc(F.conv2d(x, w, None, padding=padding)), _nhwc(F.conv2d(x.abs(), w.abs(), None, padding=padding))
+
+
+def epilogue_bound(terms, K, bias, out_dtype, extra=None, rounds=1):
+    """(ref64, bound64) from (ref, A) ``terms`` of a K-term sum, with
+    ``bias`` [c] and ``extra`` (NCHW: the accumulated y0 or the residual)
+    added: one more term each."""
+    ref, A = terms
+    if bias is not None:
+        ref, A, K = ref + bias.double(), A + bias.double().abs(), K + 1
+    if extra is not None:
+        e = _nhwc(extra.double())
+        ref, A, K = ref + e, A + e.abs(), K + 1
+    return _finish(ref, A, K, out_dtype, rounds)
+
+
+def conv_bound(x, w, bias, padding, out_dtype, extra=None, rounds=1):
+    """3x3 (padding 1) or 1x1 (padding 0) convolution of x [n, cin, h, w]
+    with w [cout, cin, k, k]: K = k k cin (+ 1 per bias / extra)."""
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    return epilogue_bound(conv_terms(x, w, padding), K, bias, out_dtype, extra, rounds)
+
+
+def conv1x1_bound(x, w, bias, out_dtype, extra=None):
+    """K = cin"""
+    return conv_bound(x, w, bias, 0, out_dtype, extra)
+
+
+def convt_up_bound(x, w, bias, out_dtype):
+    """ConvTranspose2d(k 2, stride 2) forward of x [n, cin, h, w] with
+    w [cin, cout, 2, 2]: every output pixel has one tap, K = cin (+ 1)."""
+    x, w = x.double(), w.double()
+    ref = _nhwc(F.conv_transpose2d(x, w, None, stride=2))
+    A = _nhwc(F.conv_transpose2d(x.abs(), w.abs(), None, stride=2))
+    return epilogue_bound((ref, A), w.shape[0], bias, out_dtype)
+
+
+def convt_down_bound(g, w, out_dtype):
+    """its input grad: g [n, cout, 2h, 2w] gathered 2x2 with w [cin, cout, 2,
+    2], K = 4 cout terms (the channels of the gathered operand)."""
+    g, w = g.double(), w.double()
+    ref = _nhwc(F.conv2d(g, w, None, stride=2))
+    A = _nhwc(F.conv2d(g.abs(), w.abs(), None, stride=2))
+    return _finish(ref, A, 4 * w.shape[1], out_dtype, 1)
+
+
+def _wgrad64(x, dy, k):
+    n, ci, h, w = x.shape
+    co = dy.shape[1]
+    p = k // 2
+    xp = F.pad(x, (p, p, p, p))
+    g = dy.permute(1, 0, 2, 3).reshape(co, -1)
+    out = torch.empty(co, ci, k, k, dtype=torch.float64)
+    for ky in range(k):
+        for kx in range(k):
+            xs = xp[:, :, ky:ky + h, kx:kx + w].permute(1, 0, 2, 3).reshape(ci, -1)
+            out[:, :, ky, kx] = g @ xs.t()
+    return out
+
+
+def wgrad_bound(x, dy, k, dw0=None):
+    """conv weight grad dW[co][ci][ky][kx] = sum_p dy[p, co] x[p + tap, ci]
+    (fp32 output, torch's layout) of x [n, cin, h, w], dy [n, cout, h, w]:
+    K = n h w (+ 1 with ``dw0`` accumulated into)."""
+    x, dy = x.double(), dy.double()
+    ref, A = _wgrad64(x, dy, k), _wgrad64(x.abs(), dy.abs(), k)
+    K = x.shape[0] * x.shape[2] * x.shape[3]
+    if dw0 is not None:
+        ref, A, K = ref + dw0.double(), A + dw0.double().abs(), K + 1
+    return _finish(ref, A, K, torch.float32, 1)
+
+
+def relu(rb):
+    return rb[0].clamp_min(0), rb[1]
+
+
+def prelu(rb, alpha):
+    assert abs(alpha) <= 1
+    return torch.where(rb[0] > 0, rb[0], alpha * rb[0]), rb[1]
+
+
+def masked(rb, mask):
+    """result * (mask > 0), mask NCHW, a tensor of its own"""
+    return torch.where(_nhwc(mask) > 0, rb[0], torch.zeros((), dtype=torch.float64)), rb[1]
+
+
+def pooled(rb):
+    """MaxPool2d(2), floor sizes: the max of ref, and of the bound, per window"""
+    def mp(t):
+        return F.max_pool2d(t.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1).contiguous()
+    return mp(rb[0]), mp(rb[1])
+
+
+def stats_bound(terms, K):
+    """BN statistics of the pre-bias sum, (ref64, bound64) [c, 2] =
+    (sum, sum of squares) per channel, from (ref, A) NHWC ``terms``."""
+    ref, A = terms
+    c = ref.shape[-1]
+    r, e = ref.reshape(-1, c), (2.0 * K * U * A).reshape(-1, c)
+    P = r.shape[0]
+    s_ref, q_ref = r.sum(0), (r * r).sum(0)
+    s_b = e.sum(0) + 2.0 * P * U * r.abs().sum(0)
+    q_b = (2.0 * r.abs() * e + e * e).sum(0) + 2.0 * P * U * q_ref
+    return torch.stack((s_ref, q_ref), 1), torch.stack((s_b, q_b), 1)
+
+
+# ---------------------------------------------------------------------------
+# guard bands
+
+class Guarded:
+    """the whole buffer of a guarded tensor: ``raw`` = band | tensor | band"""
+
+    def __init__(self, raw, band, poison):
+        self.raw, self.band, self.poison = raw, band, poison
+
+
+def default_band(shape, dtype):
+    """two full image rows of an NHWC tensor (2 w c elements; the last two
+    extents of any other shape), at least 256 bytes, rounded up to a multiple
+    of 256 bytes: a walk one halo row too far stays inside the buffer, and the
+    view keeps the alignment of a fresh allocation"""
+    item = torch.empty((), dtype=dtype).element_size()
+    rows = 2 * int(shape[-1]) * (int(shape[-2]) if len(shape) > 1 else 1)
+    nbytes = -(-max(rows * item, 256) // 256) * 256
+    return nbytes // item
+
+
+def guarded(shape, dtype, dev, fill=None, band=None, poison=SENTINEL):
+    """(buf, view): ``view`` of ``shape`` inside a larger buffer whose bands
+    before and after it hold ``poison`` -- the finite SENTINEL for an output
+    (check it with ``intact``), NaN for an input (a read past the tensor that
+    reaches a result makes it NaN).  The interior is ``fill``, or NaN where
+    none is given: an element a non-accumulating kernel never writes then fails
+    ``assert_within``.  (Integer dtypes: bands 0xA5; default interior 0xFF,
+    which no window index equals and which reads as NaN in an fp32 workspace.)"""
+    numel = 1
+    for s in shape:
+        numel *= int(s)
+    band = default_band(shape, dtype) if band is None else int(band)
+    fp = dtype.is_floating_point
+    if not fp:
+        poison = 0xA5
+    raw = torch.full((numel + 2 * band,), poison, dtype=dtype, device=dev)
+    view = raw[band:band + numel].view(shape)
+    if fill is not None:
+        view.copy_(fill)
+    else:
+        view.fill_(math.nan if fp else 0xFF)
+    assert not raw.is_cuda or view.data_ptr() % 256 == 0
+    return Guarded(raw, band, poison), view
+
+
+def intact(buf):
+    """both bands of a ``guarded`` buffer still hold their poison"""
+    lo, hi = buf.raw[:buf.band], buf.raw[buf.raw.numel() - buf.band:]
+    if isinstance(buf.poison, float) and math.isnan(buf.poison):
+        return bool(torch.isnan(lo).all() and torch.isnan(hi).all())
+    want = torch.full((), buf.poison, dtype=buf.raw.dtype, device=buf.raw.device)
+    return bool((lo == want).all() and (hi == want).all())
