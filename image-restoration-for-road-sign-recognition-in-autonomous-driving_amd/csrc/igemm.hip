@@ -1146,9 +1146,10 @@ ConvRoute conv_route(const rr_igemm_desc *d, const RrPath &p, int kind) {
   return r;
 }
 
-// rows of the BN statistics partial slab rr_igemm writes for *d; the
-// BN-backward partial slabs (rr_igemm_bnbwd) are sized with it too, from the
-// plain call's route of the same descriptor
+// rows of the BN statistics partial slab rr_igemm writes for *d: the plain
+// call's route.  (The BN-backward partial slabs follow the kernel
+// rr_igemm_bnbwd launches, which is another route where the plain call takes
+// stream1 or a stream3 strip instance: rr_igemm_bnbwd_rows.)
 extern "C" int rr_igemm_stat_blocks(const rr_igemm_desc *d) {
   if (!d) return RR_EINVAL;
   return conv_route(d, rr_path_read(), CK_PLAIN).rows;
@@ -1363,9 +1364,17 @@ static size_t bnbwd_bytes(const rr_igemm_desc *d, int rows) {
   return ((size_t)rows * d->c_out * 3 + (size_t)rows * (d->c_out / 64)) * sizeof(float);
 }
 
+// rows of the partial slabs rr_igemm_bnbwd writes for *d: those of the kernel
+// it launches (the CK_BNBWD route; host-only, descriptors the call rejects
+// included)
+extern "C" int rr_igemm_bnbwd_rows(const rr_igemm_desc *d) {
+  if (!d) return RR_EINVAL;
+  return conv_route(d, rr_path_read(), CK_BNBWD).rows;
+}
+
 extern "C" size_t rr_igemm_bnbwd_workspace(const rr_igemm_desc *d) {
   if (!d || d->c_out <= 0) return 0;
-  const int rows = rr_igemm_stat_blocks(d);
+  const int rows = rr_igemm_bnbwd_rows(d);
   return rows <= 0 ? 0 : bnbwd_bytes(d, rows);
 }
 
@@ -1389,9 +1398,9 @@ extern "C" int rr_igemm_bnbwd(const rr_igemm_desc *d, const void *dy, const void
   a.bt = (const char *)t;
   a.bmean = mean; a.binv = invstd; a.baff_s = aff_s; a.baff_b = aff_b; a.balpha = alpha;
   a.bpart = partial;
-  // (the alpha partials follow the rows the caller sized the slabs with:
-  // rr_igemm_stat_blocks, the plain call's route)
-  a.bapart = partial + (size_t)conv_route(d, p, CK_PLAIN).rows * d->c_out * 3;
+  // (the alpha partials follow the rows the launched kernel writes, which is
+  // what the caller sized the slabs with: rr_igemm_bnbwd_rows)
+  a.bapart = partial + (size_t)r.rows * d->c_out * 3;
   hipStream_t st = (hipStream_t)stream;
   if (r.family == CF_STREAM3) {
     S3Args s{};

@@ -109,6 +109,7 @@ _SIGS = {
     "rr_wgrad_pre_ok": (I_, [C.POINTER(WgradDesc)]),
     "rr_wgrad_pre": (I_, [C.POINTER(WgradDesc), P_, P_, P_, P_, P_, P_, P_, S_, P_]),
     "rr_wgrad_kernel_name": (C.c_char_p, [C.POINTER(WgradDesc)]),
+    "rr_igemm_bnbwd_rows": (I_, [C.POINTER(IgemmDesc)]),
     "rr_igemm_bnbwd_workspace": (S_, [C.POINTER(IgemmDesc)]),
     "rr_igemm_bnbwd": (I_, [C.POINTER(IgemmDesc), P_, P_, P_, P_, P_, P_, P_, P_, P_, P_, P_]),
     "rr_wgrad_workspace": (S_, [C.POINTER(WgradDesc)]),

@@ -571,7 +571,7 @@ def igemm_bnbwd(mode, dy, n, h, w, wpack, cout, t, mean, inv, aff_s, aff_b, alph
     d = IgemmDesc(rr_dtype(dt), mode, n, h, w, dy.shape[-1], 0, cout, 0, 0, 0, 0, 0, 0, 0)
     if out is None:
         out = torch.empty((n, h, w, cout), dtype=dt, device=dy.device)
-    rows = lib().rr_igemm_stat_blocks(C.byref(d))
+    rows = lib().rr_igemm_bnbwd_rows(C.byref(d))       # of the kernel the fused call launches
     nbytes = lib().rr_igemm_bnbwd_workspace(C.byref(d))
     part = torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
 

@@ -145,7 +145,9 @@ int rr_igemm_pre_ok(const rr_igemm_desc *d);
 int rr_igemm_pre(const rr_igemm_desc *d, const void *x1, const void *w, const float *bias,
                  const float *pre_scale, const float *pre_shift, const float *pre_alpha,
                  void *y1, float *stats_partial, rr_stream stream);
-/* number of row blocks the partial stats buffer holds: [blocks][c_out][2] */
+/* number of row blocks the partial stats buffer of rr_igemm holds:
+ * [blocks][c_out][2] (the plain call's kernel; rr_igemm_bnbwd's slabs have
+ * rr_igemm_bnbwd_rows rows) */
 int rr_igemm_stat_blocks(const rr_igemm_desc *d);
 /* The kernel rr_igemm (bnbwd = 0) or rr_igemm_bnbwd (bnbwd = 1) launches for
  * *d, e.g. "stream3_kernel<64>", "igemm3_halo_kernel<64,32>",
@@ -160,10 +162,16 @@ const char *rr_igemm_kernel_name(const rr_igemm_desc *d, int bnbwd);
  *   gm = g * (u > 0 ? 1 : alpha),  u = t * aff_s[c] + aff_b[c] (BN output)
  * to gm_out and the partials partial[rows][c_out][3] = {sum gm, sum gm*xhat, 0}
  * (xhat = (t - mean) * invstd) followed by partial_alpha[rows][c_out/64] of
- * sum(g * u * (u <= 0)), rows = rr_igemm_stat_blocks(d).  Replaces the
+ * sum(g * u * (u <= 0)), rows = rr_igemm_bnbwd_rows(d): the partial rows of
+ * the kernel rr_igemm_bnbwd launches (rr_igemm_kernel_name(d, 1)), which is
+ * not rr_igemm_stat_blocks(d) where the plain call takes a kernel the fused
+ * one has no instance of (the 1x1 streaming kernel, the 3x3 column strips).
+ * rr_igemm_bnbwd_workspace(d) = (rows * c_out * 3 + rows * (c_out / 64)) * 4
+ * bytes holds both slabs.  Host-only queries, no launch.  Replaces the
  * separate rr_bn_bwd_reduce pass (mask_kind 2) over dL/d(PReLU out).
  * d: no bias / split / mask / accumulate / stats / act, c_in2 = 0,
  * c_out % 64 == 0. */
+int rr_igemm_bnbwd_rows(const rr_igemm_desc *d);
 size_t rr_igemm_bnbwd_workspace(const rr_igemm_desc *d);
 int rr_igemm_bnbwd(const rr_igemm_desc *d, const void *dy, const void *w, const void *t,
                    const float *mean, const float *invstd, const float *aff_s,

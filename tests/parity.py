@@ -237,6 +237,166 @@ def stats_bound(terms, K):
 
 
 # ---------------------------------------------------------------------------
+# the fused BN / PReLU backward epilogues
+#
+# rr_igemm_bnbwd works on the fp32 accumulator g of a dgrad (pixel p, channel
+# c; e_p = 2 K u A_p its bound as above):
+#   u_p  = t_p s + b                  fp32, contracted to an fma or not
+#   gm_p = u_p > 0 ? g_p : alpha g_p  stored in the compute dtype
+#   column sums over the pixels of sum gm and sum gm xhat, xhat_p = (t_p -
+#   mean) invstd, of the unrounded gm, in fp32; and sum over u_p <= 0 of
+#   g_p u_p over pixels AND channels, the products in fp32, the sum in fp64.
+#
+# The sign of u.  Everything is a function of sign(u_p).  t is bf16-exact (8
+# significand bits) and s is fp32 (24), so t s is exact in fp64; rounded to
+# fp32 once after adding b it is the fma's u, rounded twice the unfused one.
+# ``sign_ambiguous`` marks the elements where the two disagree or either is
+# zero; the tests fix their inputs so that there are none, and then the mask
+# is a tensor of its own (|m| <= 1, 1-Lipschitz) and gm keeps the bound of g.
+#
+# Column sums (the model is stats_bound).  |gm_p - ref_p| <= e_p; the factor 2
+# in e_p leaves K u A_p >= K u |g_p|, K >= 64, which covers the rounding of
+# alpha g, the two roundings of xhat_p and the one of gm_p xhat_p (3 u
+# |gm_p xhat_p|).  P fp32 terms summed in any order add (P - 1) u sum|term|:
+#   sum gm:       sum_p e_p          + P u sum_p |gm_p|
+#   sum gm xhat:  sum_p e_p |xhat_p| + P u sum_p |gm_p xhat_p|
+# (The row-streaming kernel sums gm t and forms invstd (sum gm t - mean sum gm)
+# per workgroup: its worst case has |t_p| + |mean| where this has |t_p - mean|.
+# It is held to the same, tighter, bound.)
+#
+# The alpha partial, N = P c terms: sum_{u <= 0} e_p |u_p| for the accumulator,
+# and N 2^-53 sum|g_p u_p| for the fp64 summation:
+#   sum_{u <= 0} e_p |u_p| + N 2^-53 sum |g_p u_p|
+# Three fp32 roundings have no term of their own: the fp32 u_p is within d_p =
+# 2 u (|t_p s| + |b|) of the exact one either way (|g_p| d_p), the product
+# g_p u_p is rounded once and each row's fp64 sum once to fp32 (2 u |g_p u_p|).
+# They are inside the K u A_p |u_p| the factor 2 of e_p leaves over, summed
+# over the elements -- not element by element where u_p cancels -- and
+# bnbwd_bounds asserts that for its inputs.
+# (The row-streaming kernel sums these in fp32; it is held to the same bound.)
+
+def sign_ambiguous(t, s, b):
+    """elements of t [..., c] (bf16-exact, fp32) whose fp32 u = t s + b has
+    another sign as an fma than as a product and a sum, or is zero either way"""
+    t, s, b = t.float(), s.float(), b.float()
+    two = t * s + b                                             # two roundings
+    one = (t.double() * s.double() + b.double()).float()        # one (the product is exact in fp64)
+    return ((two > 0) != (one > 0)) | (two == 0) | (one == 0)
+
+
+def make_sign_unambiguous(t, s, b, dtype=torch.bfloat16):
+    """t with every ambiguous element moved to the neighbouring value of
+    ``dtype`` away from zero (repeated until none is left); exact in ``dtype``
+    in and out"""
+    ity = torch.int16 if dtype == torch.bfloat16 else torch.int32
+    t = t.float().clone()
+    for _ in range(4):
+        bad = sign_ambiguous(t, s, b)
+        if not bool(bad.any()):
+            break
+        nxt = (t.to(dtype).view(ity) + 1).view(dtype).float()       # sign-magnitude: one ulp away from zero
+        t = torch.where(bad, nxt, t)
+    return t
+
+
+def bnbwd_bounds(terms, K, t, mean, invstd, aff_s, aff_b, alpha, out_dtype):
+    """(ref64, bound64) of gm [n, h, w, c], of the column sums [c, 2] = (sum
+    gm, sum gm xhat) and of the alpha sum (0-d), from (ref, A) NHWC ``terms``
+    of the K-term dgrad and t NHWC; no element of t may be sign-ambiguous."""
+    assert abs(alpha) <= 1
+    g, A = terms
+    e = 2.0 * K * U * A
+    t, s, b = t.double(), aff_s.double(), aff_b.double()
+    u = t * s + b
+    neg = ~(u > 0)
+    gm = torch.where(neg, alpha * g, g)
+    xhat = (t - mean.double()) * invstd.double()
+    c = g.shape[-1]
+    P = g.numel() // c
+
+    def col(x):
+        return x.reshape(-1, c).sum(0)
+    tx = gm * xhat
+    sums = torch.stack((col(gm), col(tx)), 1)
+    sums_b = torch.stack((col(e) + P * U * col(gm.abs()), col(e * xhat.abs()) + P * U * col(tx.abs())), 1)
+    gu = torch.where(neg, g * u, torch.zeros((), dtype=torch.float64))
+    zero = torch.zeros((), dtype=torch.float64)
+    a_b = torch.where(neg, e * u.abs(), zero).sum() + g.numel() * 2.0 ** -53 * gu.abs().sum()
+    # the roundings of u, of g u and of each row's store, inside what the factor 2 of e leaves over
+    du = 2.0 * U * ((t * s).abs() + b.abs())
+    assert float(torch.where(neg, g.abs() * du + 2.0 * U * gu.abs(), zero).sum()) <= 0.5 * float(
+        torch.where(neg, e * u.abs(), zero).sum())
+    return {"gm": (gm, _round_term(gm, out_dtype, 1) + e), "sums": (sums, sums_b), "alpha": (gu.sum(), a_b)}
+
+
+def cast32(rb):
+    """a value inside (ref, bound) in fp64, rounded once to fp32 (the
+    finalize's dgamma / dbeta / dalpha from its fp64 sums of the partial rows;
+    the fp64 sum of R fp32 rows adds R 2^-53 of the magnitudes, inside the u)"""
+    ref, bound = rb
+    return ref, bound + 2.0 * U * (ref.abs() + bound)
+
+
+def _stored(ref, ev, out_dtype):
+    """the bound of a value within ev of ref after one store in ``out_dtype``"""
+    if out_dtype == torch.float32:
+        return ev
+    assert out_dtype == torch.bfloat16
+    return ev + HALF_ULP_BF16 * (ref.abs() + ev)
+
+
+def affine_prelu_bound(t, s, b, alpha, out_dtype):
+    """rr_affine_act: y = PReLU(t s + b) of t NHWC, stored in ``out_dtype``.
+    The fp32 u is within 2 u (|t s| + |b|) of the exact one (fma or not), the
+    slope is one more fp32 product, PReLU with |alpha| <= 1 is 1-Lipschitz;
+    then one store: half an ulp of a value within ev of ref."""
+    assert abs(alpha) <= 1
+    t, s, b = t.double(), s.double(), b.double()
+    u = t * s + b
+    ref = torch.where(u > 0, u, alpha * u)
+    ev = 2.0 * U * ((t * s).abs() + b.abs()) + U * ref.abs()
+    return ref, _stored(ref, ev, out_dtype)
+
+
+def pool_bwd_bounds(g, pdy, idx, aux, t, mean, invstd, gamma, out_dtype, sum_stored):
+    """The BN backward behind a ReLU and a 2x2 max-pool (mask kind 3), all
+    NHWC: gt = g + unpool(pdy, idx) (the window position idx = 2 dy + dx gets
+    the pooled grad; one fp32 add, u |gt|), gm = gt (aux > 0), the column sums
+    [c, 2] = (sum gm, sum gm xhat) of the unrounded gm -- of the stored gm with
+    ``sum_stored`` (rr_bn_bwd_reduce_gm) -- and the apply
+      dt = a (gm - m0 - xhat m1),  a = gamma invstd, m0 = sum gm / P, m1 = sum gm xhat / P.
+    Bounds: e_p = u |gm_p|, or the stored gm's bound where the stored value
+    is what is summed and what the apply reads; the sums as bnbwd_bounds; dt =
+    a gm + (-a invstd m1) t + a (mean invstd m1 - m0) evaluated in fp32 from
+    fp32 coefficients: a e_p, the sums' bounds over P, 8 u of the magnitudes
+    of its terms (6 coefficient and 2 fma roundings), one store."""
+    g, pdy, t = g.double(), pdy.double(), t.double()
+    n, h, w, c = g.shape
+    up = torch.zeros_like(g)
+    win = up.view(n, h // 2, 2, w // 2, 2, c)
+    for k in range(4):
+        win[:, :, k // 2, :, k % 2, :] = torch.where(idx == k, pdy, torch.zeros((), dtype=torch.float64))
+    gt = g + up
+    gm = torch.where(aux > 0, gt, torch.zeros((), dtype=torch.float64))
+    gm_b = _stored(gm, U * gm.abs(), out_dtype)
+    e = gm_b if sum_stored else U * gm.abs()
+    P = n * h * w
+    xhat = (t - mean.double()) * invstd.double()
+
+    def col(x):
+        return x.reshape(-1, c).sum(0)
+    tx = gm * xhat
+    sums = torch.stack((col(gm), col(tx)), 1)
+    sums_b = torch.stack((col(e) + P * U * col(gm.abs()), col(e * xhat.abs()) + P * U * col(tx.abs())), 1)
+    a = gamma.double() * invstd.double()
+    m0, m1 = sums[:, 0] / P, sums[:, 1] / P
+    dt = a * (gm - m0 - xhat * m1)
+    mag = a.abs() * (gm.abs() + m0.abs() + m1.abs() * invstd.double() * (t.abs() + mean.double().abs()))
+    ev = a.abs() * (e + sums_b[:, 0] / P + xhat.abs() * sums_b[:, 1] / P) + 8.0 * U * mag
+    return {"gm": (gm, gm_b), "sums": (sums, sums_b), "dt": (dt, _stored(dt, ev, out_dtype))}
+
+
+# ---------------------------------------------------------------------------
 # guard bands
 
 class Guarded:

@@ -1,10 +1,14 @@
 """The routing sweep: every host-only routing query of the library (kernel
 names, BN partial rows, workspace sizes, *_ok) over the descriptors the models
 and tests use, under the RR_PATH settings the parity tests force.  No launch,
-no GPU.  tests/test_routing_cpu.py compares it with the table recorded from
-the build before the routing became one decision per call
-(tests/golden/routing_*.json); run this file to print a digest table, or with
-a path argument to write the full table there (for locating a mismatch)."""
+no GPU.  tests/test_routing_cpu.py compares it with the recorded tables
+(tests/golden/routing_*.json: the build before the routing became one decision
+per call, with the BN-backward slab columns as of the build that sizes them
+from the launched kernel); run this file to print a
+digest table, with a path argument to write the full table there (for locating
+a mismatch), or with --golden to rewrite routing_sweep_digest.json and
+routing_model_rows.json from the loaded library (routing_pool_names.json is
+the record of an older query and is never rewritten)."""
 import ctypes as C
 import hashlib
 import json
@@ -39,9 +43,12 @@ def _lib():
 
 def conv_table(keys=False, geoms=GEOMS, chans=CHANS, modes=(0, 1, 2, 3)):
     """Rows [name, bnbwd name, stat blocks, bnbwd workspace, dgrad_sc name,
-    pre_ok] under the current RR_PATH (keys: the descriptor in front)."""
+    pre_ok, bnbwd rows] under the current RR_PATH (keys: the descriptor in
+    front).  A library loaded with RR_LIB_PATH that predates
+    rr_igemm_bnbwd_rows gives the rows without that last column."""
     from roadrestore._lib import IgemmDesc
     L = _lib()
+    bnbwd_rows = getattr(L, "rr_igemm_bnbwd_rows", None)
     rows = []
     for dt in (0, 1):
         for mode in modes:
@@ -53,6 +60,8 @@ def conv_table(keys=False, geoms=GEOMS, chans=CHANS, modes=(0, 1, 2, 3)):
                         r = [L.rr_igemm_kernel_name(p, 0).decode(), L.rr_igemm_kernel_name(p, 1).decode(),
                              L.rr_igemm_stat_blocks(p), L.rr_igemm_bnbwd_workspace(p),
                              L.rr_igemm_dgrad_sc_kernel_name(p, 64).decode(), L.rr_igemm_pre_ok(p)]
+                        if bnbwd_rows is not None:
+                            r.append(bnbwd_rows(p))
                         rows.append([dt, mode, n, h, w, c1, c2, co, *f] + r if keys else r)
     return rows
 
@@ -101,6 +110,30 @@ def with_path(path, fn):
             os.environ["RR_PATH"] = old
 
 
+def launched_bnbwd_rows(d, path):
+    """The partial rows of the kernel rr_igemm_bnbwd launches for d under
+    RR_PATH=path, measured without rr_igemm_bnbwd_rows: rr_igemm_stat_blocks
+    under a setting where the plain call names that same kernel (the family
+    the fused call has no instance of switched off).  Returns (rows, plain
+    name, bnbwd name, plain rows)."""
+    L = _lib()
+    p = C.byref(d)
+
+    def ask():
+        return (L.rr_igemm_kernel_name(p, 0).decode(), L.rr_igemm_kernel_name(p, 1).decode(),
+                L.rr_igemm_stat_blocks(p))
+    plain, fused, plain_rows = with_path(path, ask)
+    rows = plain_rows if plain == fused else None
+    for off in ("stream3_strips=0", "stream1=0"):
+        if rows is None:
+            got = with_path((path + "," if path else "") + off, ask)
+            if got[0] == fused:
+                assert got[1] == fused
+                rows = got[2]
+    assert rows is not None, (path, plain, fused)
+    return rows, plain, fused, plain_rows
+
+
 def record(full_path=None):
     """The golden files' content from the loaded library: (digests, model rows,
     pool names); full_path: also write every row there."""
@@ -116,7 +149,7 @@ def record(full_path=None):
              for p in MODEL_PATHS}
     names, pool = [], {}
     for p in PATHS:
-        got = with_path(p, lambda: [L.rr_igemm_pool_kernel_name(C.byref(d)).decode() for d in pool_descs()])
+        got = with_path(p, lambda: [L.rr_igemm_pool_kernel_name(C.byref(d), 1).decode() for d in pool_descs()])
         for g in got:
             if g not in names:
                 names.append(g)
@@ -131,5 +164,15 @@ if __name__ == "__main__":
     import sys
     sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), p) for p in
                     ("image-restoration-for-road-sign-recognition-in-autonomous-driving_amd", "")]
-    dg, _, _ = record(sys.argv[1] if len(sys.argv) > 1 else None)
+    args = [a for a in sys.argv[1:] if a != "--golden"]
+    dg, model, _ = record(args[0] if args else None)
     print(json.dumps(dg, indent=1))
+    if "--golden" in sys.argv[1:]:
+        gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+        with open(os.path.join(gold, "routing_sweep_digest.json"), "w") as f:
+            f.write(json.dumps(dg, indent=1) + "\n")
+        with open(os.path.join(gold, "routing_model_rows.json"), "w") as f:   # one row per line
+            f.write("{\n" + ",\n".join(
+                json.dumps(p) + ": {\n" + ",\n".join(
+                    json.dumps(k) + ": [\n" + ",\n".join("  " + json.dumps(r) for r in rows) + "\n]"
+                    for k, rows in t.items()) + "\n}" for p, t in model.items()) + "\n}\n")

@@ -329,6 +329,12 @@ def test_stream3_column_strips_selected(monkeypatch):
     assert name(2, 224, 224, stats=1) == "conv3r_kernel<s2,64>"    # training epilogues: tap-reuse
     assert name(2, 224, 224, mask=1) == "conv3r_kernel<s2,64>"
     assert name(2, 224, 224, bnbwd=True) == "conv3r_kernel<s2,64>"
+    # ... whose partial rows, not the strip kernel's 256, size the BN-backward slabs
+    import ctypes as C
+    import roadrestore as rr
+    d = IgemmDesc(RR_BF16, RR_CONV3X3, 2, 224, 224, 64, 0, 64, 0, 0, 0, 0, 0, 0, 0)
+    assert rr_stat_blocks(d) == 256 and rr.lib().rr_igemm_bnbwd_rows(C.byref(d)) == 784
+    assert rr.lib().rr_igemm_bnbwd_workspace(C.byref(d)) == (784 * 64 * 3 + 784) * 4
     assert name(16, 64, 64, stats=1) == "stream3_kernel<64>"
     assert name(4, 104, 160) == "stream3_kernel<s32>"
     assert name(16, 64, 64) == "stream3_kernel<64>"

@@ -21,10 +21,11 @@ library will launch, and calls the C ABI directly on buffers of its own:
     against an fp64 CPU reference of bf16-exact (fp32 mode: fp32) operands.
 Shapes are the smallest that keep each kernel instance (found with the
 host-only name query, which needs no GPU); the fp64 reference of a shape is
-computed once and shared by its epilogues.  The fused calls whose in-kernel
-bf16 rounding of an intermediate the bound does not model (rr_igemm_pre,
-rr_wgrad_pre, rr_igemm_bnbwd, rr_igemm_dgrad_sc) get the bands and the
-unwritten-element check only; their numbers are checked in their own files."""
+computed once and shared by its epilogues.  The fused calls (rr_igemm_pre,
+rr_wgrad_pre, rr_igemm_bnbwd, rr_igemm_dgrad_sc, the BN backward with the pool
+backward folded in) get the bands and the unwritten-element check here; every
+element of theirs is held to a derived bound in
+tests/test_fused_elementwise_gpu.py."""
 import ctypes as C
 import math
 
@@ -441,7 +442,8 @@ def test_wgrad_elementwise(dev, case, acc, monkeypatch):
 
 
 # ---------------------------------------------------------------------------
-# canary-only: the fused calls (bands and the unwritten-element check)
+# the fused calls: bands and the unwritten-element check (their per-element
+# bounds: tests/test_fused_elementwise_gpu.py)
 
 def _finite_and_intact(bufs, what):
     for key, (buf, view) in bufs.items():
@@ -496,7 +498,8 @@ def test_igemm_pre_and_wgrad_pre_canary(dev, shape, monkeypatch):
 ], ids=["stream3", "conv3r-rows", "conv3r-seg", "halo"])
 def test_igemm_bnbwd_canary(dev, path, shape, prefix, monkeypatch):
     """rr_igemm_bnbwd: the dgrad with the BN / PReLU backward reduce in its
-    epilogue; gm and the partial rows (sized by rr_igemm_bnbwd_workspace)"""
+    epilogue; gm and the partial rows (rr_igemm_bnbwd_rows of them, sized by
+    rr_igemm_bnbwd_workspace)"""
     import roadrestore as rr
     from roadrestore import ops
     from roadrestore._lib import IgemmDesc
@@ -523,7 +526,8 @@ def test_igemm_bnbwd_canary(dev, path, shape, prefix, monkeypatch):
         assert parity.intact(buf), f"a store outside {key}"
     assert bool(torch.isfinite(outs["gm"][1].float()).all())
     # partial rows [rows][c][3] (the third column unused) + alpha rows: no NaN written
-    rows = L.rr_igemm_stat_blocks(C.byref(desc))
+    rows = L.rr_igemm_bnbwd_rows(C.byref(desc))
+    assert need == (rows * cc * 3 + rows * (cc // 64)) * 4
     part = outs["partial"][1][:rows * cc * 3].view(rows, cc, 3)
     assert bool(torch.isfinite(part[..., :2]).all())
 

@@ -1,8 +1,10 @@
 """The library routes each conv / weight-grad call once (csrc/route.h
 conv_route, wgrad.hip wgrad_route): every host-only routing query over the
 sweep of tests/route_sweep.py answers what the build before that change
-answered (tests/golden/routing_*.json, recorded from it), under every RR_PATH
-setting the parity tests force.  No launch, no GPU."""
+answered (tests/golden/routing_*.json, recorded from it; the BN-backward slab
+columns re-recorded when they began to follow the kernel rr_igemm_bnbwd
+launches), under every RR_PATH setting the parity tests force.  No launch, no
+GPU."""
 import ctypes as C
 import json
 import os
@@ -22,8 +24,8 @@ def golden(name):
 @pytest.mark.parametrize("path", RS.PATHS)
 def test_routing_sweep_matches_recorded_digest(path, monkeypatch):
     """names (plain, bnbwd, dgrad_sc), statistics rows, bnbwd workspace and
-    pre_ok of every conv row; name, workspace and pre_ok of every weight-grad
-    row: SHA-256 and row count per RR_PATH setting"""
+    rows, pre_ok of every conv row; name, workspace and pre_ok of every
+    weight-grad row: SHA-256 and row count per RR_PATH setting"""
     monkeypatch.setenv("RR_PATH", path)
     want = golden("routing_sweep_digest.json")[path]
     assert RS.digest(RS.conv_table()) == want["conv"]
@@ -80,6 +82,68 @@ def test_pool_kernel_name_is_the_launched_kernel(path, monkeypatch):
         assert g0 == (c if nobias else o), (path, d.n, d.h, d.w, d.c_in1, d.c_in2, d.c_out, d.has_bias)
     if "stream3=0" not in path:
         assert nbias > 0 and (nstrip > 0) == ("stream3_strips=0" not in path)
+
+
+# geometries at which the plain call and rr_igemm_bnbwd take different kernels
+# (kept out of route_sweep.GEOMS: the recorded digests keep their meaning):
+# 3x3 column strips (plain: stream3_kernel<s32>) and, with stream1_minp=256,
+# 1x1 maps whose stream1 row count is above (2x16x16) and below (264x16x16)
+# the tiled kernel's
+BNBWD_GEOMS = [(4, 176, 96), (2, 224, 224), (2, 16, 16), (264, 16, 16)]
+BNBWD_PATHS = RS.PATHS + ["stream1_minp=256"]
+
+
+def bnbwd_descs():
+    """the descriptors of the sweep rr_igemm_bnbwd accepts: 3x3 / 1x1, the
+    all-zero flag set, one source, whole 64-channel column tiles"""
+    from roadrestore._lib import IgemmDesc
+    for dt in (0, 1):
+        for mode in (0, 1):
+            for (n, h, w) in RS.GEOMS + [g for g in BNBWD_GEOMS if g not in RS.GEOMS]:
+                for (c1, c2, co) in RS.CHANS:
+                    if c2 == 0 and co % 64 == 0:
+                        yield IgemmDesc(dt, mode, n, h, w, c1, 0, co, 0, 0, 0, 0, 0, 0, 0)
+
+
+@pytest.mark.parametrize("path", BNBWD_PATHS)
+def test_bnbwd_slabs_follow_the_launched_kernel(path, monkeypatch):
+    """rr_igemm_bnbwd_rows / rr_igemm_bnbwd_workspace size the partial slabs
+    for the kernel rr_igemm_bnbwd launches (the CK_BNBWD route), which is not
+    the plain call's where that takes stream1 or a stream3 strip instance:
+    sized from rr_igemm_stat_blocks the launch stored past the workspace and
+    over its own alpha partials (3x3 64 -> 64 at 2x224x224: 784 rows into 256),
+    or the finalize summed rows nobody wrote (1x1 at 2x16x16 with
+    stream1_minp=256: 4 of 512).  On the build before rr_igemm_bnbwd_rows the
+    workspace equation below fails for exactly those rows: bf16 only, per
+    setting "" 53, stream3=0 47, conv3r=0 53, "stream3=0,conv3r=0" 47,
+    swgrad=0 53, "swgrad=0,wgrad_halo=0" 53, stream1=0 6, conv3r_wg=8 53,
+    stream3_strips=0 47, stream1_minp=256 193 of the 1188 descriptors (6 of
+    them 3x3 column strips wherever the strips are on, the rest 1x1 stream1
+    maps)."""
+    import roadrestore
+    L = roadrestore.lib()
+    kinds = {"strip": 0, "stream1_more": 0, "stream1_fewer": 0}
+    count = 0
+    for d in bnbwd_descs():
+        rows, plain, fused, plain_rows = RS.launched_bnbwd_rows(d, path)
+        monkeypatch.setenv("RR_PATH", path)
+        key = (path, d.dtype, d.mode, d.n, d.h, d.w, d.c_in1, d.c_out, plain, fused)
+        assert rows > 0, key
+        assert L.rr_igemm_bnbwd_rows(C.byref(d)) == rows, key
+        assert L.rr_igemm_bnbwd_workspace(C.byref(d)) == (rows * d.c_out * 3 + rows * (d.c_out // 64)) * 4, key
+        count += 1
+        if plain != fused and plain_rows != rows:
+            assert plain.startswith("stream1_kernel") or plain == "stream3_kernel<s32>", key
+            if plain.startswith("stream3"):
+                kinds["strip"] += 1
+            else:
+                kinds["stream1_more" if plain_rows > rows else "stream1_fewer"] += 1
+    assert count == 2 * 2 * (len(RS.GEOMS) + 3) * 11 == 1188
+    # every mismatch kind is in the sweep
+    if path == "":
+        assert kinds["strip"] > 0, kinds
+    if path == "stream1_minp=256":
+        assert min(kinds.values()) > 0, kinds
 
 
 def _name64(L):

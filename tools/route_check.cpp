@@ -44,6 +44,7 @@ static uint64_t sweep() {
             h = fold(h, rr_igemm_kernel_name(&d, 0));
             h = fold(h, rr_igemm_kernel_name(&d, 1));
             h = fold(h, (uint64_t)rr_igemm_stat_blocks(&d));
+            h = fold(h, (uint64_t)rr_igemm_bnbwd_rows(&d));
             h = fold(h, (uint64_t)rr_igemm_bnbwd_workspace(&d));
             h = fold(h, rr_igemm_pool_kernel_name(&d, 0));
             h = fold(h, rr_igemm_pool_kernel_name(&d, 1));
