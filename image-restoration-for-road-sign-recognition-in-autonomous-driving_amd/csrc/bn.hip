@@ -949,28 +949,22 @@ extern "C" int rr_affine_act(int dtype, long long P, int C, const void *x, const
   hipStream_t st = (hipStream_t)stream;
   if (C % 8 == 0 && 256 % (C / 8) == 0) {
     const int grid8 = rr_grid_cap((P * C / 8 + 255) / 256, RR_EW_GRID);
-    if (dtype == RR_BF16)
-      hipLaunchKernelGGL(affine_act8_kernel<bf16_t>, dim3(grid8), dim3(256), 0, st, P, C,
-                         (const bf16_t *)x, scale, shift, alpha, (const bf16_t *)res, res_scale,
-                         res_shift, relu, (bf16_t *)y);
-    else
-      hipLaunchKernelGGL(affine_act8_kernel<float>, dim3(grid8), dim3(256), 0, st, P, C,
-                         (const float *)x, scale, shift, alpha, (const float *)res, res_scale,
-                         res_shift, relu, (float *)y);
-    RR_CHECK_LAUNCH();
-    return RR_OK;
+    return rr_dispatch_elt(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL(affine_act8_kernel<T>, dim3(grid8), dim3(256), 0, st, P, C, (const T *)x,
+                         scale, shift, alpha, (const T *)res, res_scale, res_shift, relu, (T *)y);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
   }
   const int grid = rr_grid_cap((P * C / 4 + 255) / 256, 4096);
-  if (dtype == RR_BF16)
-    hipLaunchKernelGGL(affine_act_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, P, C,
-                       (const bf16_t *)x, scale, shift, alpha, (const bf16_t *)res, res_scale,
-                       res_shift, relu, (bf16_t *)y);
-  else
-    hipLaunchKernelGGL(affine_act_kernel<float>, dim3(grid), dim3(256), 0, st, P, C,
-                       (const float *)x, scale, shift, alpha, (const float *)res, res_scale,
-                       res_shift, relu, (float *)y);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_elt(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(affine_act_kernel<T>, dim3(grid), dim3(256), 0, st, P, C, (const T *)x, scale,
+                       shift, alpha, (const T *)res, res_scale, res_shift, relu, (T *)y);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 extern "C" int rr_affine_act_pool(int dtype, int n, int h, int w, int C, const void *x,
@@ -984,16 +978,13 @@ extern "C" int rr_affine_act_pool(int dtype, int n, int h, int w, int C, const v
   const long long total = (long long)n * (h / 2) * (w / 2) * (C / 8);
   const int grid = rr_grid_cap((total + 255) / 256, 8192);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RR_BF16)
-    hipLaunchKernelGGL(affine_act_pool_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, n, h, w, C,
-                       (const bf16_t *)x, scale, shift, (const bf16_t *)res, res_scale, res_shift, relu,
-                       (bf16_t *)y, (bf16_t *)y_pool, idx);
-  else
-    hipLaunchKernelGGL(affine_act_pool_kernel<float>, dim3(grid), dim3(256), 0, st, n, h, w, C,
-                       (const float *)x, scale, shift, (const float *)res, res_scale, res_shift, relu,
-                       (float *)y, (float *)y_pool, idx);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_elt(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(affine_act_pool_kernel<T>, dim3(grid), dim3(256), 0, st, n, h, w, C, (const T *)x,
+                       scale, shift, (const T *)res, res_scale, res_shift, relu, (T *)y, (T *)y_pool, idx);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 extern "C" int rr_bn_bwd_blocks(const rr_bnbwd_desc *d) {
@@ -1008,6 +999,7 @@ static double bnbwd_count(const rr_bnbwd_desc *d) {
 
 static int bnbwd_check(const rr_bnbwd_desc *d) {
   if (!d || d->P <= 0 || d->C <= 0 || d->C % 4 || d->C / 4 > 256) return RR_EINVAL;
+  if (!rr_dtype_ok(d->dtype)) return RR_EINVAL;
   if (d->nbn != 1 && d->nbn != 2) return RR_EINVAL;
   if (d->mask_kind < 0 || d->mask_kind > 5) return RR_EINVAL;
   if (d->mask_kind >= 4 && (d->nbn != 2 || d->C % 8 || 256 % (d->C / 8)))
@@ -1056,29 +1048,30 @@ extern "C" int rr_bn_bwd_reduce(const rr_bnbwd_desc *d, const void *g, const voi
   if (d->C % 8 == 0 && 256 % (d->C / 8) == 0) {
     const size_t shm8 = ((size_t)(256 / (d->C / 8)) * d->C * 3 + 256) * sizeof(float);
     float *ap = d->mask_kind == 2 ? apart : nullptr;
-#define RR_RED8(TT, M, N) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<TT, M, N>), dim3(blocks), dim3(256), shm8, st, a, partial, ap, rpb)
-#define RR_RED8_T(TT)                                             \
-    switch (d->mask_kind * 2 + (d->nbn - 1)) {                    \
-      case 0: RR_RED8(TT, 0, 1); break; case 1: RR_RED8(TT, 0, 2); break; \
-      case 2: RR_RED8(TT, 1, 1); break; case 3: RR_RED8(TT, 1, 2); break; \
-      case 4: RR_RED8(TT, 2, 1); break; case 5: RR_RED8(TT, 2, 2); break; \
-      case 6: RR_RED8(TT, 3, 1); break; case 7: RR_RED8(TT, 3, 2); break; \
-      case 9: RR_RED8(TT, 4, 2); break; default: RR_RED8(TT, 5, 2); break; \
-    }
-    if (d->dtype == RR_BF16) { RR_RED8_T(bf16_t) } else { RR_RED8_T(float) }
-#undef RR_RED8_T
-#undef RR_RED8
+    return rr_dispatch_elt(d->dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      return rr_dispatch_int<0, 1, 2, 3, 4, 5>(d->mask_kind, [&](auto m) {
+        return rr_dispatch_int<1, 2>(d->nbn, [&](auto nb) {
+          constexpr int M = decltype(m)::value, N = decltype(nb)::value;
+          if constexpr (M < 4 || N == 2) {      // kinds 4 and 5: two BNs only (bnbwd_check)
+            hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, M, N>), dim3(blocks), dim3(256), shm8, st, a,
+                               partial, ap, rpb);
+            RR_CHECK_LAUNCH();
+            return RR_OK;
+          } else {
+            return RR_EINVAL;
+          }
+        });
+      });
+    });
+  }
+  return rr_dispatch_elt(d->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(blocks), dim3(256), shm, st, a, partial,
+                       d->mask_kind == 2 ? apart : nullptr, rpb);
     RR_CHECK_LAUNCH();
     return RR_OK;
-  }
-  if (d->dtype == RR_BF16)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(blocks), dim3(256), shm, st, a, partial,
-                       d->mask_kind == 2 ? apart : nullptr, rpb);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(blocks), dim3(256), shm, st, a, partial,
-                       d->mask_kind == 2 ? apart : nullptr, rpb);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  });
 }
 
 extern "C" int rr_bn_bwd_reduce_gm(const rr_bnbwd_desc *d, const void *g, const void *aux,
@@ -1095,15 +1088,15 @@ extern "C" int rr_bn_bwd_reduce_gm(const rr_bnbwd_desc *d, const void *g, const 
   const long long rpb = (d->P + blocks - 1) / blocks;
   const size_t shm8 = ((size_t)(256 / (d->C / 8)) * d->C * 3 + 256) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-#define RR_REDGM(TT, M) hipLaunchKernelGGL((bn_bwd_reduce8_kernel<TT, M, 1, true>), dim3(blocks), dim3(256), shm8, st, a, partial, nullptr, rpb, (TT *)gm_out)
-  if (d->dtype == RR_BF16) {
-    if (d->mask_kind == 1) RR_REDGM(bf16_t, 1); else RR_REDGM(bf16_t, 3);
-  } else {
-    if (d->mask_kind == 1) RR_REDGM(float, 1); else RR_REDGM(float, 3);
-  }
-#undef RR_REDGM
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_elt(d->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return rr_dispatch_int<1, 3>(d->mask_kind, [&](auto m) {
+      hipLaunchKernelGGL((bn_bwd_reduce8_kernel<T, decltype(m)::value, 1, true>), dim3(blocks), dim3(256),
+                         shm8, st, a, partial, nullptr, rpb, (T *)gm_out);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
+  });
 }
 
 extern "C" int rr_bn_bwd_finalize(const rr_bnbwd_desc *d, const float *partial,
@@ -1138,30 +1131,32 @@ extern "C" int rr_bn_bwd_apply(const rr_bnbwd_desc *d, const void *g, const void
   hipStream_t st = (hipStream_t)stream;
   if (d->C % 8 == 0 && 256 % (d->C / 8) == 0) {
     const int grid8 = rr_grid_cap((d->P * d->C / 8 + 255) / 256, RR_EW_GRID);
-#define RR_APP8(TT, M, N, GM) hipLaunchKernelGGL((bn_bwd_apply8_kernel<TT, M, N, GM>), dim3(grid8), dim3(256), 0, st, a, coef, (TT *)dt0, (TT *)dt1, (TT *)gm_out)
-#define RR_APP8_M(TT, M)                                                        \
-    if (d->nbn == 1) { if (gm_out) RR_APP8(TT, M, 1, true); else RR_APP8(TT, M, 1, false); } \
-    else { if (gm_out) RR_APP8(TT, M, 2, true); else RR_APP8(TT, M, 2, false); }
-#define RR_APP8_T(TT)                                                           \
-    if (d->mask_kind == 0) { RR_APP8_M(TT, 0) } else if (d->mask_kind == 1) { RR_APP8_M(TT, 1) } \
-    else if (d->mask_kind == 2) { RR_APP8_M(TT, 2) } else if (d->mask_kind == 3) { RR_APP8_M(TT, 3) } \
-    else if (d->mask_kind == 4) { RR_APP8(TT, 4, 2, false); } else { RR_APP8(TT, 5, 2, false); }
-    if (d->dtype == RR_BF16) { RR_APP8_T(bf16_t) } else { RR_APP8_T(float) }
-#undef RR_APP8_T
-#undef RR_APP8_M
-#undef RR_APP8
-    RR_CHECK_LAUNCH();
-    return RR_OK;
+    return rr_dispatch_elt(d->dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      return rr_dispatch_int<0, 1, 2, 3, 4, 5>(d->mask_kind, [&](auto m) {
+        auto launch = [&](auto nb, auto gm) {
+          hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, decltype(m)::value, decltype(nb)::value, decltype(gm)::value>),
+                             dim3(grid8), dim3(256), 0, st, a, coef, (T *)dt0, (T *)dt1, (T *)gm_out);
+          RR_CHECK_LAUNCH();
+          return RR_OK;
+        };
+        if constexpr (decltype(m)::value >= 4)  // kinds 4 and 5: two BNs, no gm_out (checked above)
+          return launch(ic<2>{}, std::false_type{});
+        else
+          return rr_dispatch_int<1, 2>(d->nbn, [&](auto nb) {
+            return gm_out ? launch(nb, std::true_type{}) : launch(nb, std::false_type{});
+          });
+      });
+    });
   }
   const int grid = rr_grid_cap((d->P * d->C / 4 + 255) / 256, 4096);
-  if (d->dtype == RR_BF16)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, a, coef,
-                       (bf16_t *)dt0, (bf16_t *)dt1, (bf16_t *)gm_out);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid), dim3(256), 0, st, a, coef,
-                       (float *)dt0, (float *)dt1, (float *)gm_out);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_elt(d->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid), dim3(256), 0, st, a, coef, (T *)dt0, (T *)dt1,
+                       (T *)gm_out);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 // the residual-tail BN backward apply of a block whose output feeds the final
@@ -1184,14 +1179,13 @@ extern "C" int rr_bn_bwd_apply_convout(const rr_bnbwd_desc *d, int h, int w, con
   a.h = h; a.w = w; a.cody = dy; a.cow = wt;
   const int grid8 = rr_grid_cap((d->P * d->C / 8 + 255) / 256, RR_EW_GRID);
   hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == RR_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply8_kernel<bf16_t, 4, 2, false, true>), dim3(grid8), dim3(256), 0, st, a, coef,
-                       (bf16_t *)dt0, (bf16_t *)dt1, (bf16_t *)nullptr);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply8_kernel<float, 4, 2, false, true>), dim3(grid8), dim3(256), 0, st, a, coef,
-                       (float *)dt0, (float *)dt1, (float *)nullptr);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_elt(d->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((bn_bwd_apply8_kernel<T, 4, 2, false, true>), dim3(grid8), dim3(256), 0, st, a, coef,
+                       (T *)dt0, (T *)dt1, (T *)nullptr);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 extern "C" size_t rr_channel_sum_workspace(long long P, int C) {
@@ -1207,13 +1201,14 @@ extern "C" int rr_channel_sum(int dtype, long long P, int C, const void *x, floa
   const int R = 256 / (C / 4);
   const size_t shm = (size_t)R * C * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RR_BF16)
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3(blocks), dim3(256), shm, st, P, C,
-                       (const bf16_t *)x, (float *)ws, rpb);
-  else
-    hipLaunchKernelGGL(colsum_kernel<float>, dim3(blocks), dim3(256), shm, st, P, C,
-                       (const float *)x, (float *)ws, rpb);
-  RR_CHECK_LAUNCH();
+  const int rc = rr_dispatch_elt(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(colsum_kernel<T>, dim3(blocks), dim3(256), shm, st, P, C, (const T *)x,
+                       (float *)ws, rpb);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
+  if (rc != RR_OK) return rc;
   hipLaunchKernelGGL(colsum_finalize, dim3((C + 15) / 16), dim3(256), 0, st, C, blocks,
                      (const float *)ws, out, accumulate);
   RR_CHECK_LAUNCH();
@@ -1230,14 +1225,13 @@ extern "C" int rr_bn_stats(int dtype, long long P, int C, const void *x, float *
   const int R = 256 / (C / 4);
   const size_t shm = (size_t)R * C * 2 * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RR_BF16)
-    hipLaunchKernelGGL(colstats_kernel<bf16_t>, dim3(blocks), dim3(256), shm, st, P, C,
-                       (const bf16_t *)x, partial, rpb);
-  else
-    hipLaunchKernelGGL(colstats_kernel<float>, dim3(blocks), dim3(256), shm, st, P, C,
-                       (const float *)x, partial, rpb);
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_elt(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(colstats_kernel<T>, dim3(blocks), dim3(256), shm, st, P, C, (const T *)x, partial,
+                       rpb);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 // at most this many partial rows: the single-launch finalize (measured 5-7 us

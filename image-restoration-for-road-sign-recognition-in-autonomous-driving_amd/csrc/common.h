@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/roadrestore.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -158,6 +160,28 @@ __device__ __forceinline__ float wave_sum(float v) {
   do {                                                      \
     if (hipGetLastError() != hipSuccess) return RR_ELAUNCH; \
   } while (0)
+
+// ---- run-time value -> template argument, for the launch wrappers (host) ----
+// A wrapper writes its launch once, in a generic lambda that takes the tag
+// (using T = typename decltype(tag)::type; launch k<T>; RR_CHECK_LAUNCH();
+// return RR_OK).  Any other dtype, or an integer outside Vs, is RR_EINVAL and
+// the lambda does not run: nothing is launched.  if constexpr inside keeps a
+// nested dispatch from instantiating kernels no call reaches.  An entry point
+// with an earlier return (empty tensor, RR_EUNSUPPORTED) or without a typed
+// launch tests rr_dtype_ok itself.
+static inline bool rr_dtype_ok(int dtype) { return dtype == RR_BF16 || dtype == RR_F32; }
+template <int N> using ic = std::integral_constant<int, N>;
+template <typename T> struct EltTag { using type = T; };
+template <typename F> static inline int rr_dispatch_elt(int dtype, F &&f) {
+  if (dtype == RR_BF16) return f(EltTag<bf16_t>{});
+  if (dtype == RR_F32) return f(EltTag<float>{});
+  return RR_EINVAL;
+}
+template <int... Vs, typename F> static inline int rr_dispatch_int(int v, F &&f) {
+  int r = RR_EINVAL;
+  (void)(... || (v == Vs && ((r = f(ic<Vs>{})), true)));
+  return r;
+}
 
 // Kernel-path overrides for the parity tests, the library's one run-time
 // knob: RR_PATH="key=value[,key=value...]".  Every default is the

@@ -143,8 +143,6 @@ struct C3EpiStamp {
 #define VM_BARRIER(N) vm_barrier<N>()
 #endif
 
-template <int N> using ic = std::integral_constant<int, N>;
-
 // EPI: 0 = every epilogue (operand loads: accumulate / residual / ReLU mask,
 // PReLU, pool, the fused BN backward), 1 = bias, statistics, ReLU and the
 // concat split only -- the forward and plain dgrad of the training step,

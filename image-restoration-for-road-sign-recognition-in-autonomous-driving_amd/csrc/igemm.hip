@@ -985,15 +985,11 @@ int launch_mode(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
   const long long nblk = npblk * a.ncblk;
   if (nblk > 0x7fffffffLL) return RR_EUNSUPPORTED;
   dim3 grid((unsigned)nblk), block(256);
-  switch (d->mode) {
-    case RR_CONV3X3: hipLaunchKernelGGL((igemm_kernel<T, BC, BP, WC, RR_CONV3X3>), grid, block, 0, st, a); break;
-    case RR_CONV1X1: hipLaunchKernelGGL((igemm_kernel<T, BC, BP, WC, RR_CONV1X1>), grid, block, 0, st, a); break;
-    case RR_CONVT_UP: hipLaunchKernelGGL((igemm_kernel<T, BC, BP, WC, RR_CONVT_UP>), grid, block, 0, st, a); break;
-    case RR_CONVT_DOWN: hipLaunchKernelGGL((igemm_kernel<T, BC, BP, WC, RR_CONVT_DOWN>), grid, block, 0, st, a); break;
-    default: return RR_EINVAL;
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_int<RR_CONV3X3, RR_CONV1X1, RR_CONVT_UP, RR_CONVT_DOWN>(d->mode, [&](auto mode) {
+    hipLaunchKernelGGL((igemm_kernel<T, BC, BP, WC, decltype(mode)::value>), grid, block, 0, st, a);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 // tile choice: (BC, BP) -- the stat-partial row block is BP pixels
@@ -1040,14 +1036,11 @@ int launch_halo(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
   if constexpr (BC < 64) {
     if (a.cin == 64 && a.ncblk == 1 && nblk > 512) grid = dim3(512);
   }
-  switch (d->w) {
-    case 64: hipLaunchKernelGGL((igemm3_halo_kernel<BC, 64, RR_CONV3X3, BP, NT>), grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((igemm3_halo_kernel<BC, 32, RR_CONV3X3, BP, NT>), grid, block, 0, st, a); break;
-    case 16: hipLaunchKernelGGL((igemm3_halo_kernel<BC, 16, RR_CONV3X3, BP, NT>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((igemm3_halo_kernel<BC, 8, RR_CONV3X3, BP, NT>), grid, block, 0, st, a); break;
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_int<64, 32, 16, 8>(d->w, [&](auto w) {   // halo_bc: one of these
+    hipLaunchKernelGGL((igemm3_halo_kernel<BC, decltype(w)::value, RR_CONV3X3, BP, NT>), grid, block, 0, st, a);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 template <typename T>
@@ -1064,7 +1057,7 @@ int dispatch(const rr_igemm_desc *d, IgemmArgs &a, const ConvRoute &r, hipStream
     if (r.halo_bc == 64) return launch_halo<64, 256>(d, a, st);
     return launch_halo<16, 256>(d, a, st);
   }
-  return d->dtype == RR_BF16 ? launch_tiled<bf16_t>(d, a, r, st) : launch_tiled<float>(d, a, r, st);
+  return rr_dispatch_elt(d->dtype, [&](auto tag) { return launch_tiled<typename decltype(tag)::type>(d, a, r, st); });
 }
 
 const char *halo_name(int hb, int w) {
@@ -1159,7 +1152,7 @@ static int fill_args(const rr_igemm_desc *d, const void *x1, const void *x2, con
                      const float *bias, void *y1, void *y2, const void *mask,
                      float *stats_partial, IgemmArgs &a) {
   if (!d || !x1 || !w || !y1) return RR_EINVAL;
-  if (d->dtype != RR_F32 && d->dtype != RR_BF16) return RR_EINVAL;
+  if (!rr_dtype_ok(d->dtype)) return RR_EINVAL;
   const int bk = d->dtype == RR_F32 ? 32 : 64;
   if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c_out <= 0 || d->c_in1 <= 0) return RR_EINVAL;
   if (d->c_in1 % bk || d->c_in2 % bk) return RR_EUNSUPPORTED;
@@ -1243,7 +1236,7 @@ extern "C" int rr_igemm_ex(const rr_igemm_desc *d, const void *x1, const void *x
                            const float *bias, const float *alpha, const void *res, void *y1,
                            void *y_pool, const void *mask, float *stats_partial, rr_stream stream) {
   const int all = RR_ACT_RELU | RR_ACT_PRELU | RR_ACT_RES | RR_ACT_POOL | RR_ACT_NOFULL;
-  if (!d || d->act < 0 || (d->act & ~all) || (d->act & 3) == 3) return RR_EINVAL;
+  if (!d || !rr_dtype_ok(d->dtype) || d->act < 0 || (d->act & ~all) || (d->act & 3) == 3) return RR_EINVAL;
   if ((d->act & 3) == RR_ACT_PRELU && !alpha) return RR_EINVAL;
   if ((d->act & RR_ACT_RES) && (!res || d->out_split || d->accumulate || d->out_nchw)) return RR_EINVAL;
   if ((d->act & RR_ACT_POOL) && (!y_pool || d->out_split || d->h < 2 || d->w < 2)) return RR_EINVAL;
@@ -1290,6 +1283,7 @@ extern "C" int rr_igemm_pre(const rr_igemm_desc *d, const void *x1, const void *
                             void *y1, float *stats_partial, rr_stream stream) {
   if (!d || !x1 || !w || !bias || !pre_scale || !pre_shift || !pre_alpha || !y1 || !stats_partial)
     return RR_EINVAL;
+  if (!rr_dtype_ok(d->dtype)) return RR_EINVAL;
   const ConvRoute r = conv_route(d, rr_path_read(), CK_PRE);
   if (r.family != CF_STREAM3) return RR_EUNSUPPORTED;
   S3Args s{};
@@ -1308,7 +1302,7 @@ extern "C" int rr_igemm_pre(const rr_igemm_desc *d, const void *x1, const void *
 // epilogue
 extern "C" int rr_igemm_pool(const rr_igemm_desc *d, const void *x1, const void *x2, const void *w,
                              const float *bias, void *y_pool, uint8_t *pool_idx, rr_stream stream) {
-  if (!d || !y_pool || !pool_desc_ok(d)) return RR_EINVAL;
+  if (!d || !y_pool || !pool_desc_ok(d) || !rr_dtype_ok(d->dtype)) return RR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const ConvRoute r = conv_route(d, rr_path_read(), pool_idx ? CK_POOL_IDX : CK_POOL);
   if (r.family == CF_STREAM3) {
@@ -1345,7 +1339,7 @@ extern "C" int rr_igemm_dgrad_sc(const rr_igemm_desc *d, const void *dy, const v
                                  const void *dy_sc, const void *w_sc, int c_sc, void *y,
                                  rr_stream stream) {
   if (!d || !dy || !w || !dy_sc || !w_sc || !y || c_sc <= 0) return RR_EINVAL;
-  if (!sc_desc_ok(d)) return RR_EINVAL;
+  if (!sc_desc_ok(d) || !rr_dtype_ok(d->dtype)) return RR_EINVAL;
   const ConvRoute r = conv_route(d, rr_path_read(), CK_DGRAD_SC);
   if (c_sc != 64 || r.family != CF_STREAM3) return RR_EUNSUPPORTED;
   S3Args s{};

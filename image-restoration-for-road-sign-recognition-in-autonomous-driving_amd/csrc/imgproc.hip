@@ -545,18 +545,13 @@ extern "C" int rr_resize_bilinear_u8(int n, int h, int w, int c, int oh, int ow,
     }
     const long long np = (long long)n * h * w;
     const dim3 g(rr_grid_cap((np + 255) / 256, 8192)), b(256);
-#define RS_SAME(CC)                                                                                 \
-  if (out_kind == 0) hipLaunchKernelGGL((rs_same_kernel<CC, 0>), g, b, 0, st, np, h * w, in, out, nm, 0); \
-  else hipLaunchKernelGGL((rs_same_kernel<CC, 1>), g, b, 0, st, np, h * w, in, out, nm, mean != nullptr);
-    switch (c) {
-      case 1: RS_SAME(1) break;
-      case 2: RS_SAME(2) break;
-      case 3: RS_SAME(3) break;
-      default: RS_SAME(4) break;
-    }
-#undef RS_SAME
-    RR_CHECK_LAUNCH();
-    return RR_OK;
+    return rr_dispatch_int<1, 2, 3, 4>(c, [&](auto cc) {
+      constexpr int CC = decltype(cc)::value;
+      if (out_kind == 0) hipLaunchKernelGGL((rs_same_kernel<CC, 0>), g, b, 0, st, np, h * w, in, out, nm, 0);
+      else hipLaunchKernelGGL((rs_same_kernel<CC, 1>), g, b, 0, st, np, h * w, in, out, nm, mean != nullptr);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
   }
   char *base = (char *)ws;
   RsAxis ah{w, ow, p.kh, (int *)(base + p.off_bh), (int *)(base + p.off_kh)};
@@ -572,24 +567,19 @@ extern "C" int rr_resize_bilinear_u8(int n, int h, int w, int c, int oh, int ow,
     nm.std[i] = std ? std[i] : 1.f;
   }
   const int norm = mean != nullptr;
-#define RS_LAUNCH(CC)                                                                              \
-  hipLaunchKernelGGL(rs_horiz_kernel<CC>, gh, b, 0, st, n, h, w, ow, p.y_first, p.rows, p.kh,    \
-                     ah.bounds, ah.kk, in, tmp);                                                   \
-  if (out_kind == 0)                                                                               \
-    hipLaunchKernelGGL((rs_vert_kernel<CC, 0>), gv, b, 0, st, n, p.rows, oh, ow, p.kv, p.y_first, \
-                       av.bounds, av.kk, tmp, out, nm, norm);                                      \
-  else                                                                                             \
-    hipLaunchKernelGGL((rs_vert_kernel<CC, 1>), gv, b, 0, st, n, p.rows, oh, ow, p.kv, p.y_first, \
-                       av.bounds, av.kk, tmp, out, nm, norm);
-  switch (c) {
-    case 1: RS_LAUNCH(1) break;
-    case 2: RS_LAUNCH(2) break;
-    case 3: RS_LAUNCH(3) break;
-    default: RS_LAUNCH(4) break;
-  }
-#undef RS_LAUNCH
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_int<1, 2, 3, 4>(c, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    hipLaunchKernelGGL(rs_horiz_kernel<CC>, gh, b, 0, st, n, h, w, ow, p.y_first, p.rows, p.kh, ah.bounds,
+                       ah.kk, in, tmp);
+    if (out_kind == 0)
+      hipLaunchKernelGGL((rs_vert_kernel<CC, 0>), gv, b, 0, st, n, p.rows, oh, ow, p.kv, p.y_first,
+                         av.bounds, av.kk, tmp, out, nm, norm);
+    else
+      hipLaunchKernelGGL((rs_vert_kernel<CC, 1>), gv, b, 0, st, n, p.rows, oh, ow, p.kv, p.y_first,
+                         av.bounds, av.kk, tmp, out, nm, norm);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 extern "C" int rr_ragged_check(int n, int c, size_t in_bytes, const rr_ragged_image *images_host,
@@ -632,18 +622,13 @@ extern "C" int rr_resize_ragged_u8(int n, int c, int max_h, int max_w, int oh, i
   }
   const int norm = mean != nullptr;
   const dim3 g((unsigned)((long long)n * ((oh + p.band - 1) / p.band))), b(RG_T);
-#define RG_LAUNCH(CC)                                                                              \
-  if (out_kind == 0) hipLaunchKernelGGL((rg_resample_kernel<CC, 0>), g, b, p.lds, st, a, out, nm, norm); \
-  else hipLaunchKernelGGL((rg_resample_kernel<CC, 1>), g, b, p.lds, st, a, out, nm, norm);
-  switch (c) {
-    case 1: RG_LAUNCH(1) break;
-    case 2: RG_LAUNCH(2) break;
-    case 3: RG_LAUNCH(3) break;
-    default: RG_LAUNCH(4) break;
-  }
-#undef RG_LAUNCH
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_int<1, 2, 3, 4>(c, [&](auto cc) {
+    constexpr int CC = decltype(cc)::value;
+    if (out_kind == 0) hipLaunchKernelGGL((rg_resample_kernel<CC, 0>), g, b, p.lds, st, a, out, nm, norm);
+    else hipLaunchKernelGGL((rg_resample_kernel<CC, 1>), g, b, p.lds, st, a, out, nm, norm);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 extern "C" int rr_cv_resize_linear_u8(int n, int h, int w, int c, int oh, int ow,
@@ -667,14 +652,12 @@ extern "C" int rr_cv_resize_linear_u8(int n, int h, int w, int c, int oh, int ow
   while (ve < width - simd_lanes / 2) ve += simd_lanes / 2;
   const long long total = (long long)n * oh * ow;
   const dim3 g(rr_grid_cap((total + 255) / 256, 8192)), b(256);
-  switch (c) {
-    case 1: hipLaunchKernelGGL(cv_resize_linear_kernel<1>, g, b, 0, st, n, h, w, oh, ow, sxs, sys, ve, in, out); break;
-    case 2: hipLaunchKernelGGL(cv_resize_linear_kernel<2>, g, b, 0, st, n, h, w, oh, ow, sxs, sys, ve, in, out); break;
-    case 3: hipLaunchKernelGGL(cv_resize_linear_kernel<3>, g, b, 0, st, n, h, w, oh, ow, sxs, sys, ve, in, out); break;
-    default: hipLaunchKernelGGL(cv_resize_linear_kernel<4>, g, b, 0, st, n, h, w, oh, ow, sxs, sys, ve, in, out); break;
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_int<1, 2, 3, 4>(c, [&](auto cc) {
+    hipLaunchKernelGGL(cv_resize_linear_kernel<decltype(cc)::value>, g, b, 0, st, n, h, w, oh, ow, sxs, sys,
+                       ve, in, out);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 extern "C" size_t rr_ssim_workspace(int n, int c) {

@@ -488,7 +488,7 @@ __global__ void sgd_step_inc_kernel(int64_t *step) { *step += 1; }
 extern "C" int rr_linear_wgrad(int dtype, int n, int fin, int fout, const void *dy, const void *x,
                                float *dw, float *db, int accumulate, rr_stream stream) {
   if (!dy || !x || !dw || n <= 0 || fin <= 0 || fout <= 0) return RR_EINVAL;
-  if (dtype != RR_F32 && dtype != RR_BF16) return RR_EINVAL;
+  if (!rr_dtype_ok(dtype)) return RR_EINVAL;
   if (misaligned16(dy) || misaligned16(x) || misaligned16(dw)) return RR_EINVAL;
   if (fin % 64) return RR_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -506,7 +506,7 @@ extern "C" int rr_linear_wgrad(int dtype, int n, int fin, int fout, const void *
 extern "C" int rr_linear_dgrad(int dtype, int n, int fin, int fout, const void *dy, const void *w,
                                const float *mask, float *dx, rr_stream stream) {
   if (!dy || !w || !dx || n <= 0 || fin <= 0 || fout <= 0) return RR_EINVAL;
-  if (dtype != RR_F32 && dtype != RR_BF16) return RR_EINVAL;
+  if (!rr_dtype_ok(dtype)) return RR_EINVAL;
   if (misaligned16(dy) || misaligned16(w) || misaligned16(dx) || misaligned16(mask)) return RR_EINVAL;
   if (fin % 64) return RR_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;

@@ -192,8 +192,6 @@ __device__ __forceinline__ uint2 pack4(f32x4 g) {
   return o;
 }
 
-template <int N> using ic = std::integral_constant<int, N>;
-
 // a wave's MP 16-pixel blocks of a step: block ni sits brow(ni) image rows and
 // bcol(ni) columns from the wave's first pixel (POOL: 2 rows x 8 MP columns,
 // blocks 2j / 2j + 1 = rows 0 / 1 of columns 16 j ..)

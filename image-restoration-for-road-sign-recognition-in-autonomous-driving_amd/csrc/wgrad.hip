@@ -320,8 +320,6 @@ struct Halo3Args {
 // columns {x..x+3, x+8..x+11} of one row) or by column bit 1 and row parity
 // (W = 8: columns {x..x+3} of two consecutive rows).  The DMA writes a row's
 // 16-B slots in lane order, so a lane fetches the chunk its slot holds.
-template <int N> using ic = std::integral_constant<int, N>;
-
 template <int OFF> __device__ __forceinline__ s16x4 tr_read(uint32_t addr) {
   static_assert(OFF >= 0 && OFF < 65536, "ds offset");
   s16x4 r;
@@ -634,13 +632,11 @@ static void launch_reduce(const float *ws, float *dw, int CA, int CB, int taps, 
   int G = 1;
   while (G < 16 && G * 2 <= nsplit && (total / 4 + 256 / G - 1) / (256 / G) < 1024) G *= 2;
   const unsigned nb = (unsigned)((total / 4 + 256 / G - 1) / (256 / G));
-  switch (G) {
-    case 1: hipLaunchKernelGGL(wgrad_reduce_g<1>, dim3(nb), dim3(256), 0, st, ws, dw, CA, CB, taps, nsplit, accumulate, alayout); break;
-    case 2: hipLaunchKernelGGL(wgrad_reduce_g<2>, dim3(nb), dim3(256), 0, st, ws, dw, CA, CB, taps, nsplit, accumulate, alayout); break;
-    case 4: hipLaunchKernelGGL(wgrad_reduce_g<4>, dim3(nb), dim3(256), 0, st, ws, dw, CA, CB, taps, nsplit, accumulate, alayout); break;
-    case 8: hipLaunchKernelGGL(wgrad_reduce_g<8>, dim3(nb), dim3(256), 0, st, ws, dw, CA, CB, taps, nsplit, accumulate, alayout); break;
-    default: hipLaunchKernelGGL(wgrad_reduce_g<16>, dim3(nb), dim3(256), 0, st, ws, dw, CA, CB, taps, nsplit, accumulate, alayout); break;
-  }
+  (void)rr_dispatch_int<1, 2, 4, 8, 16>(G, [&](auto g) {
+    hipLaunchKernelGGL(wgrad_reduce_g<decltype(g)::value>, dim3(nb), dim3(256), 0, st, ws, dw, CA, CB, taps,
+                       nsplit, accumulate, alayout);
+    return RR_OK;
+  });
 }
 
 struct Plan {
@@ -689,14 +685,11 @@ template <typename T, int BA, int BB>
 int launch(const rr_wgrad_desc *d, const Plan &pl, WgradArgs &a, hipStream_t st) {
   const long long nblk = (long long)pl.nablk * pl.nbblk * pl.taps * pl.nsplit;
   dim3 grid((unsigned)nblk), block(256);
-  switch (d->mode) {
-    case RR_CONV3X3: hipLaunchKernelGGL((wgrad_kernel<T, BA, BB, RR_CONV3X3>), grid, block, 0, st, a); break;
-    case RR_CONV1X1: hipLaunchKernelGGL((wgrad_kernel<T, BA, BB, RR_CONV1X1>), grid, block, 0, st, a); break;
-    case RR_CONVT_UP: hipLaunchKernelGGL((wgrad_kernel<T, BA, BB, RR_CONVT_UP>), grid, block, 0, st, a); break;
-    default: return RR_EINVAL;
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  return rr_dispatch_int<RR_CONV3X3, RR_CONV1X1, RR_CONVT_UP>(d->mode, [&](auto mode) {
+    hipLaunchKernelGGL((wgrad_kernel<T, BA, BB, decltype(mode)::value>), grid, block, 0, st, a);
+    RR_CHECK_LAUNCH();
+    return RR_OK;
+  });
 }
 
 template <typename T>
@@ -824,14 +817,11 @@ static int wgrad_partial(const rr_wgrad_desc *d, const WgradRoute &r, const void
     ha.nablk = ha.CA / 64; ha.nbblk = ha.CB / 64;
     ha.xcd = 1;                                  // XCD-aware workgroup order
     const dim3 grid((unsigned)(ha.nablk * ha.nbblk * r.nsplit)), block(256);
-    switch (d->w) {
-      case 64: hipLaunchKernelGGL((wgrad3_halo_kernel<64>), grid, block, 0, st, ha); break;
-      case 32: hipLaunchKernelGGL((wgrad3_halo_kernel<32>), grid, block, 0, st, ha); break;
-      case 16: hipLaunchKernelGGL((wgrad3_halo_kernel<16>), grid, block, 0, st, ha); break;
-      default: hipLaunchKernelGGL((wgrad3_halo_kernel<8>), grid, block, 0, st, ha); break;
-    }
-    RR_CHECK_LAUNCH();
-    return RR_OK;
+    return rr_dispatch_int<64, 32, 16, 8>(d->w, [&](auto w) {   // halo_ok: one of these
+      hipLaunchKernelGGL((wgrad3_halo_kernel<decltype(w)::value>), grid, block, 0, st, ha);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
   }
   const Plan &pl = r.plan;
   WgradArgs a;
@@ -851,26 +841,26 @@ static int wgrad_partial(const rr_wgrad_desc *d, const WgradRoute &r, const void
   a.xcd = 1;                                   // XCD-aware workgroup order
   a.fd_w = make_fastdiv((uint32_t)d->w);
   a.fd_hw = make_fastdiv((uint32_t)(d->h * d->w));
-  return d->dtype == RR_BF16 ? launch_t<bf16_t>(d, pl, a, st) : launch_t<float>(d, pl, a, st);
+  return rr_dispatch_elt(d->dtype, [&](auto tag) { return launch_t<typename decltype(tag)::type>(d, pl, a, st); });
 }
 
 extern "C" int rr_wgrad_partial(const rr_wgrad_desc *d, const void *dy, const void *x1,
                                 const void *x2, void *ws, size_t ws_bytes, rr_stream stream) {
-  if (!d) return RR_EINVAL;
+  if (!d || !rr_dtype_ok(d->dtype)) return RR_EINVAL;
   return wgrad_partial(d, wgrad_route(d, rr_path_read()), dy, x1, x2, nullptr, nullptr, nullptr, ws,
                        ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int rr_wgrad_reduce(const rr_wgrad_desc *d, const void *ws, size_t ws_bytes, float *dw,
                                rr_stream stream) {
-  if (!d) return RR_EINVAL;
+  if (!d || !rr_dtype_ok(d->dtype)) return RR_EINVAL;
   return wgrad_reduce(d, wgrad_route(d, rr_path_read()), ws, ws_bytes, dw, (hipStream_t)stream);
 }
 
 extern "C" int rr_wgrad(const rr_wgrad_desc *d, const void *dy, const void *x1,
                         const void *x2, float *dw, void *ws, size_t ws_bytes,
                         rr_stream stream) {
-  if (!dw || !d) return RR_EINVAL;
+  if (!dw || !d || !rr_dtype_ok(d->dtype)) return RR_EINVAL;
   const WgradRoute r = wgrad_route(d, rr_path_read());
   const int rc = wgrad_partial(d, r, dy, x1, x2, nullptr, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream);
   return rc ? rc : wgrad_reduce(d, r, ws, ws_bytes, dw, (hipStream_t)stream);
@@ -892,6 +882,7 @@ extern "C" int rr_wgrad_pre(const rr_wgrad_desc *d, const void *dy, const void *
                             const float *pre_scale, const float *pre_shift, const float *pre_alpha,
                             float *dw, void *ws, size_t ws_bytes, rr_stream stream) {
   if (!d || !dy || !x1 || !dw || !pre_scale || !pre_shift || !pre_alpha) return RR_EINVAL;
+  if (!rr_dtype_ok(d->dtype)) return RR_EINVAL;
   const WgradRoute r = wgrad_route(d, rr_path_read());
   if (!wgrad_pre_ok(d, r)) return RR_EUNSUPPORTED;
   const int rc = wgrad_partial(d, r, dy, x1, nullptr, pre_scale, pre_shift, pre_alpha, ws, ws_bytes,

@@ -40,6 +40,10 @@ enum rr_status {
   RR_EWORKSPACE = -4     /* workspace smaller than *_workspace() reported  */
 };
 
+/* Every call that launches a kernel and takes a dtype -- as an argument or in
+ * the dtype field of an rr_igemm_desc / rr_wgrad_desc / rr_bnbwd_desc --
+ * returns RR_EINVAL for any other value, before it launches anything or
+ * writes a byte. */
 enum rr_dtype { RR_F32 = 0, RR_BF16 = 1 };
 
 /* implicit-GEMM geometry (how the activation operand is gathered) */
