@@ -156,9 +156,25 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-#define RR_CHECK_LAUNCH()                                   \
-  do {                                                      \
-    if (hipGetLastError() != hipSuccess) return RR_ELAUNCH; \
+// Dry run (make launchcheck, tools/route_check.cpp): every launch of the
+// routing sources is recorded by the harness -- kernel handle, grid, block --
+// instead of performed, and never fails.  Host only, no GPU.
+#ifdef RR_DRYRUN
+extern "C" void rr_dry_launch(const void *kernel, const unsigned *grid3, const unsigned *block3);
+template <typename... A> static inline void rr_dry(const void *k, dim3 g, dim3 b, const A &...) {
+  const unsigned g3[3] = {g.x, g.y, g.z}, b3[3] = {b.x, b.y, b.z};
+  rr_dry_launch(k, g3, b3);
+}
+#undef hipLaunchKernelGGL
+#define hipLaunchKernelGGL(k, g, b, shmem, st, ...) rr_dry((const void *)(k), dim3(g), dim3(b), __VA_ARGS__)
+#define RR_LAUNCH_FAILED() false
+#else
+#define RR_LAUNCH_FAILED() (hipGetLastError() != hipSuccess)
+#endif
+
+#define RR_CHECK_LAUNCH()                        \
+  do {                                           \
+    if (RR_LAUNCH_FAILED()) return RR_ELAUNCH;   \
   } while (0)
 
 // ---- run-time value -> template argument, for the launch wrappers (host) ----
@@ -327,5 +343,5 @@ static inline int rr_colreduce(const float *in, int rows, int cols, double *out,
   const int rpc = (rows + chunks - 1) / chunks;
   hipLaunchKernelGGL(rr_colreduce_kernel, dim3((cols + 63) / 64, chunks), dim3(256), 0, st, in, rows,
                      cols, rpc, out);
-  return hipGetLastError() == hipSuccess ? chunks : -1;
+  return RR_LAUNCH_FAILED() ? -1 : chunks;
 }

@@ -841,6 +841,38 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3r_kernel(IgemmArgs a) 
   }
 }
 
+// The instantiated tile geometries: (BC, NW, NWV, HB, SG, name tag) -- column
+// block, per-wave channels, waves, halo buffers, row-segment kind (0: whole-row
+// tiles, compiled per map width 64 / 32 / 16 / 8).  r3_pick names a geometry
+// through r3_geom, which does not compile for a tuple that is not listed;
+// conv3r_launch and conv3r_name look the pick up here over all five fields.
+// The name: conv3r_kernel<W,BC> (128 x 64 wave tiles), <W,BC,32> (128 x 32);
+// row-segment tiles: <s2,BC> (32-column segments), <s1,BC> (16-column); the
+// 8-wave one-per-CU variant adds ",w8"
+#define R3_LIST(X)                                                              \
+  X(128, 64, 8, 2, 2, "128,w8") X(64, 32, 8, 2, 2, "64,w8")                     \
+  X(128, 64, 4, 1, 2, "128") X(64, 64, 4, 1, 2, "64")                           \
+  X(128, 32, 8, 2, 1, "128,w8") X(64, 32, 8, 1, 1, "64,w8")                     \
+  X(128, 32, 4, 1, 1, "128") X(64, 32, 4, 1, 1, "64")                           \
+  X(128, 64, 8, 2, 0, "128,w8") X(128, 32, 8, 2, 0, "128,32,w8")                \
+  X(64, 32, 8, 2, 0, "64,32,w8")                                                \
+  X(128, 64, 4, 1, 0, "128") X(128, 32, 4, 1, 0, "128,32")                      \
+  X(64, 64, 4, 1, 0, "64") X(64, 32, 4, 1, 0, "64,32")
+
+constexpr bool r3_is(R3Pick k, int bc, int nw, int nwv, int hb, int sg) {
+  return k.bc == bc && k.nw == nw && k.nwv == nwv && k.hb == hb && k.sg == sg;
+}
+constexpr bool r3_listed(R3Pick k) {
+#define R3_HAS(BC, NW, NWV, HB, SG, TAG) if (r3_is(k, BC, NW, NWV, HB, SG)) return true;
+  R3_LIST(R3_HAS)
+#undef R3_HAS
+  return false;
+}
+template <int BC, int NW, int NWV, int HB, int SG> constexpr R3Pick r3_geom() {
+  static_assert(r3_listed(R3Pick{BC, NW, NWV, HB, SG}), "conv3r: no instance of this geometry (R3_LIST)");
+  return R3Pick{BC, NW, NWV, HB, SG};
+}
+
 // column block and per-wave channels for *d: BC = 128 / 64 by c_out, 128 x
 // 64 wave tiles, except where that leaves fewer than 256 workgroups (one per
 // CU): the 8x8 256-channel layers (B = 512: 128 tiles) take 128 x 32 wave
@@ -874,29 +906,29 @@ R3Pick r3_pick(const rr_igemm_desc *d, const RrPath &p) {
     int nc = 0;
     if (nwv == 8) {
       if (d->c_out % 256 == 0 && W == 8 && (P / 256) * (d->c_out / 256) < 256 && P % 256 == 0) {
-        c[nc++] = {128, 32, 8, 2, 0};
+        c[nc++] = r3_geom<128, 32, 8, 2, 0>();
       } else if (d->c_out % 128 == 0) {
-        c[nc++] = {128, 64, 8, 2, 0};
+        c[nc++] = r3_geom<128, 64, 8, 2, 0>();
       } else {
-        c[nc++] = {64, 32, 8, 2, 0};
+        c[nc++] = r3_geom<64, 32, 8, 2, 0>();
       }
     } else if (d->c_out % 128 == 0) {
       // 128-channel column blocks of 128 x 64 wave tiles (256-pixel tiles);
       // below 512 workgroups (2 per CU) the 8x8 layers take 128 x 32 wave
       // tiles (128-pixel tiles)
-      if (W == 8 && (P / 256) * (d->c_out / 128) < 512 && P % 128 == 0) c[nc++] = {128, 32, 4, 1, 0};
-      else c[nc++] = {128, 64, 4, 1, 0};
+      if (W == 8 && (P / 256) * (d->c_out / 128) < 512 && P % 128 == 0) c[nc++] = r3_geom<128, 32, 4, 1, 0>();
+      else c[nc++] = r3_geom<128, 64, 4, 1, 0>();
     } else {
-      c[nc++] = {64, 64, 4, 1, 0};
+      c[nc++] = r3_geom<64, 64, 4, 1, 0>();
     }
     // batches whose pixels do not fill the first pick's tiles: smaller
     // whole-row tiles before the row-segment ones (an odd batch of 16x16
     // 256-channel maps stays on whole rows)
     if (d->c_out % 128 == 0) {
-      c[nc++] = {128, 32, 8, 2, 0};
-      c[nc++] = {128, 32, 4, 1, 0};
+      c[nc++] = r3_geom<128, 32, 8, 2, 0>();
+      c[nc++] = r3_geom<128, 32, 4, 1, 0>();
     } else {
-      c[nc++] = {64, 32, 4, 1, 0};
+      c[nc++] = r3_geom<64, 32, 4, 1, 0>();
     }
     for (int i = 0; i < nc; ++i)
       if (P % r3_tpx(c[i]) == 0) return c[i];
@@ -910,11 +942,11 @@ R3Pick r3_pick(const rr_igemm_desc *d, const RrPath &p) {
   const int fsw = p.conv3r_segwg;
   const int segwg = fsw == 4 || fsw == 8 ? fsw : (d->c_out % 128 == 0 && W <= 28 ? 8 : 4);
   if (segwg == 8) {
-    if (sg == 2) return d->c_out % 128 == 0 ? R3Pick{128, 64, 8, 2, 2} : R3Pick{64, 32, 8, 2, 2};
-    return d->c_out % 128 == 0 ? R3Pick{128, 32, 8, 2, 1} : R3Pick{64, 32, 8, 1, 1};
+    if (sg == 2) return d->c_out % 128 == 0 ? r3_geom<128, 64, 8, 2, 2>() : r3_geom<64, 32, 8, 2, 2>();
+    return d->c_out % 128 == 0 ? r3_geom<128, 32, 8, 2, 1>() : r3_geom<64, 32, 8, 1, 1>();
   }
-  if (sg == 2) return d->c_out % 128 == 0 ? R3Pick{128, 64, 4, 1, 2} : R3Pick{64, 64, 4, 1, 2};
-  return d->c_out % 128 == 0 ? R3Pick{128, 32, 4, 1, 1} : R3Pick{64, 32, 4, 1, 1};
+  if (sg == 2) return d->c_out % 128 == 0 ? r3_geom<128, 64, 4, 1, 2>() : r3_geom<64, 64, 4, 1, 2>();
+  return d->c_out % 128 == 0 ? r3_geom<128, 32, 4, 1, 1>() : r3_geom<64, 32, 4, 1, 1>();
 }
 // row-segment tiles: rows per tile, column segments and row bands per image
 int r3_tr(R3Pick k) { return (k.nwv / (k.bc / k.nw)) * (8 / k.sg); }
@@ -939,6 +971,7 @@ int conv3r_bc(const rr_igemm_desc *d, const RrPath &p, R3Pick *k) {
   if (d->c_in1 <= 0 || d->c_in1 % 32 || d->c_in2 % 32 || d->c_out % 64) return 0;
   if (d->out_split && (d->out_split % 32 || d->out_split >= d->c_out)) return 0;
   *k = r3_pick(d, p);
+  if (!r3_listed(*k)) return 0;   // (unreachable: r3_pick names listed geometries only)
   if (k->sg && p.conv3r == 2) return 0;
   const long long tiles = r3_ptiles(d, *k) * (d->c_out / k->bc);
   if (tiles <= 0 || tiles > 0x7fffffffLL) return 0;
@@ -952,98 +985,57 @@ int conv3r_rows(const rr_igemm_desc *d, R3Pick k) {
 // the specialised epilogue instances wherever the call allows one: EPI 1
 // (plain: bias / statistics / ReLU / split, no operand loads) for the
 // training step's forward and plain dgrads, 4 (+ pool), 3 (the fused BN
-// backward alone), 2 (+ accumulate / ReLU-mask operands); the general one
-// (0) otherwise
-template <int W_, int BC, int NW, int NWV, int HB, int SG>
-static void c3_launch(const IgemmArgs &a, dim3 grid, dim3 block, hipStream_t st) {
+// backward alone), 2 (+ accumulate / ReLU-mask operands), 5 (the eval
+// epilogues without operands); the general one (0) otherwise
+static int c3_epi(const IgemmArgs &a) {
   const bool plain = !a.accumulate && !a.res && !a.has_mask && (a.act & 3) != RR_ACT_PRELU &&
                      !(a.act & (RR_ACT_POOL | RR_ACT_NOFULL)) && !a.bpart;
-  if (plain) {
-    hipLaunchKernelGGL((conv3r_kernel<W_, BC, NW, NWV, HB, SG, 1>), grid, block, 0, st, a);
-    return;
-  }
+  if (plain) return 1;
   const bool ex = a.res || (a.act & 3) == RR_ACT_PRELU || (a.act & (RR_ACT_POOL | RR_ACT_NOFULL));
   if ((a.act & RR_ACT_POOL) && !a.res && (a.act & 3) != RR_ACT_PRELU && !a.accumulate && !a.has_mask &&
-      !a.bpart) {
-    hipLaunchKernelGGL((conv3r_kernel<W_, BC, NW, NWV, HB, SG, 4>), grid, block, 0, st, a);
-    return;
-  }
-  if (a.bpart && !ex && !a.accumulate && !a.has_mask) {
-    hipLaunchKernelGGL((conv3r_kernel<W_, BC, NW, NWV, HB, SG, 3>), grid, block, 0, st, a);
-    return;
-  }
-  if (!a.bpart && !ex) {
-    hipLaunchKernelGGL((conv3r_kernel<W_, BC, NW, NWV, HB, SG, 2>), grid, block, 0, st, a);
-    return;
-  }
-  if (!a.bpart && !a.accumulate && !a.has_mask) {
-    hipLaunchKernelGGL((conv3r_kernel<W_, BC, NW, NWV, HB, SG, 5>), grid, block, 0, st, a);
-    return;
-  }
-  hipLaunchKernelGGL((conv3r_kernel<W_, BC, NW, NWV, HB, SG, 0>), grid, block, 0, st, a);
+      !a.bpart)
+    return 4;
+  if (a.bpart && !ex && !a.accumulate && !a.has_mask) return 3;
+  if (!a.bpart && !ex) return 2;
+  if (!a.bpart && !a.accumulate && !a.has_mask) return 5;
+  return 0;
 }
 
 template <int BC, int NW, int NWV, int HB, int SG>
 static int conv3r_go(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
   a.ncblk = a.cout / BC;
-  const long long nblk = r3_ptiles(d, R3Pick{BC, NW, NWV, HB, SG}) * a.ncblk;
+  const long long nblk = r3_ptiles(d, r3_geom<BC, NW, NWV, HB, SG>()) * a.ncblk;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return RR_EUNSUPPORTED;
   const dim3 grid((unsigned)nblk), block(64 * NWV);
-  if constexpr (SG > 0) {
-    c3_launch<0, BC, NW, NWV, HB, SG>(a, grid, block, st);
-  } else {
-    switch (d->w) {
-      case 64: c3_launch<64, BC, NW, NWV, HB, 0>(a, grid, block, st); break;
-      case 32: c3_launch<32, BC, NW, NWV, HB, 0>(a, grid, block, st); break;
-      case 16: c3_launch<16, BC, NW, NWV, HB, 0>(a, grid, block, st); break;
-      default: c3_launch<8, BC, NW, NWV, HB, 0>(a, grid, block, st); break;
-    }
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  auto go = [&](auto w) {
+    return rr_dispatch_int<0, 1, 2, 3, 4, 5>(c3_epi(a), [&](auto epi) {
+      hipLaunchKernelGGL((conv3r_kernel<decltype(w)::value, BC, NW, NWV, HB, SG, decltype(epi)::value>), grid,
+                         block, 0, st, a);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
+  };
+  if constexpr (SG > 0) return go(ic<0>{});
+  else return rr_dispatch_int<64, 32, 16, 8>(d->w, go);   // r3_pick: whole-row tiles on these widths only
 }
 
+// a pick without an entry in R3_LIST is RR_EUNSUPPORTED, never another instance
 int conv3r_launch(const rr_igemm_desc *d, IgemmArgs &a, R3Pick k, hipStream_t st) {
-  if (k.sg == 2) {
-    if (k.nwv == 8) {
-      if (k.bc == 128) return conv3r_go<128, 64, 8, 2, 2>(d, a, st);
-      return conv3r_go<64, 32, 8, 2, 2>(d, a, st);
-    }
-    if (k.bc == 128) return conv3r_go<128, 64, 4, 1, 2>(d, a, st);
-    return conv3r_go<64, 64, 4, 1, 2>(d, a, st);
-  }
-  if (k.sg == 1) {
-    if (k.nwv == 8) {
-      if (k.bc == 128) return conv3r_go<128, 32, 8, 2, 1>(d, a, st);
-      return conv3r_go<64, 32, 8, 1, 1>(d, a, st);
-    }
-    if (k.bc == 128) return conv3r_go<128, 32, 4, 1, 1>(d, a, st);
-    return conv3r_go<64, 32, 4, 1, 1>(d, a, st);
-  }
-  if (k.nwv == 8) {
-    if (k.bc == 128 && k.nw == 64) return conv3r_go<128, 64, 8, 2, 0>(d, a, st);
-    if (k.bc == 128) return conv3r_go<128, 32, 8, 2, 0>(d, a, st);
-    return conv3r_go<64, 32, 8, 2, 0>(d, a, st);
-  }
-  if (k.bc == 128 && k.nw == 64) return conv3r_go<128, 64, 4, 1, 0>(d, a, st);
-  if (k.bc == 128) return conv3r_go<128, 32, 4, 1, 0>(d, a, st);
-  if (k.nw == 64) return conv3r_go<64, 64, 4, 1, 0>(d, a, st);
-  return conv3r_go<64, 32, 4, 1, 0>(d, a, st);
+#define R3_GO(BC, NW, NWV, HB, SG, TAG) if (r3_is(k, BC, NW, NWV, HB, SG)) return conv3r_go<BC, NW, NWV, HB, SG>(d, a, st);
+  R3_LIST(R3_GO)
+#undef R3_GO
+  return RR_EUNSUPPORTED;
 }
 
-// conv3r_kernel<W,BC> (128 x 64 wave tiles), <W,BC,32> (128 x 32); row-segment
-// tiles: <s2,BC> (32-column segments), <s1,BC> (16-column); the 8-wave
-// one-per-CU variant adds ",w8"
 const char *conv3r_name(const rr_igemm_desc *d, R3Pick k) {
-#define C3_W8(s) {"conv3r_kernel<" s ">", "conv3r_kernel<" s ",w8>"}
-#define C3_W(w) {C3_W8(#w ",64"), C3_W8(#w ",64,32"), C3_W8(#w ",128"), C3_W8(#w ",128,32")}
-  static const char *const names[4][4][2] = {C3_W(8), C3_W(16), C3_W(32), C3_W(64)};
-  static const char *const segnames[2][2][2] = {{C3_W8("s1,64"), C3_W8("s1,128")}, {C3_W8("s2,64"), C3_W8("s2,128")}};
-#undef C3_W
-#undef C3_W8
-  if (k.sg) return segnames[k.sg - 1][k.bc == 128][k.nwv == 8];
-  const int wi = d->w == 8 ? 0 : d->w == 16 ? 1 : d->w == 32 ? 2 : 3;
-  return names[wi][(k.bc == 128) * 2 + (k.nw == 32)][k.nwv == 8];
+#define R3_NAME(BC, NW, NWV, HB, SG, TAG)                                                                   \
+  if (r3_is(k, BC, NW, NWV, HB, SG))                                                                        \
+    return SG == 2 ? "conv3r_kernel<s2," TAG ">" : SG == 1 ? "conv3r_kernel<s1," TAG ">"                    \
+           : d->w == 8 ? "conv3r_kernel<8," TAG ">" : d->w == 16 ? "conv3r_kernel<16," TAG ">"              \
+           : d->w == 32 ? "conv3r_kernel<32," TAG ">" : "conv3r_kernel<64," TAG ">";
+  R3_LIST(R3_NAME)
+#undef R3_NAME
+  return "unsupported";
 }
 
 #ifdef RR_CONV3R_STAMPS

@@ -1025,8 +1025,18 @@ int halo_bc(const rr_igemm_desc *d, const RrPath &p) {
   return 0;
 }
 
-template <int BC, int BP, int NT = 2 * BP>
-int launch_halo(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
+// The instantiated LDS-halo kernels: (column block, map width), 256-pixel
+// tiles of 512 threads; and the tiled kernel's (BC, BP, WC), each for both
+// dtypes and the four modes.  The launch and the name of a route read these
+// lists: a value outside them is RR_EUNSUPPORTED / "unsupported".
+#define HALO_LIST(X)                                                                   \
+  X(128, 64) X(128, 32) X(128, 16) X(128, 8) X(64, 64) X(64, 32) X(64, 16) X(64, 8)    \
+  X(16, 64) X(16, 32) X(16, 16) X(16, 8)
+#define TILE_LIST(X) X(128, 128, 2) X(64, 256, 1) X(64, 128, 2)
+
+template <int BC, int W>
+int launch_halo(IgemmArgs &a, hipStream_t st) {
+  constexpr int BP = 256, NT = 2 * BP;
   a.ncblk = (a.cout + BC - 1) / BC;
   const long long nblk = (long long)(a.P / BP) * a.ncblk;
   if (nblk > 0x7fffffffLL) return RR_EUNSUPPORTED;
@@ -1036,45 +1046,45 @@ int launch_halo(const rr_igemm_desc *d, IgemmArgs &a, hipStream_t st) {
   if constexpr (BC < 64) {
     if (a.cin == 64 && a.ncblk == 1 && nblk > 512) grid = dim3(512);
   }
-  return rr_dispatch_int<64, 32, 16, 8>(d->w, [&](auto w) {   // halo_bc: one of these
-    hipLaunchKernelGGL((igemm3_halo_kernel<BC, decltype(w)::value, RR_CONV3X3, BP, NT>), grid, block, 0, st, a);
-    RR_CHECK_LAUNCH();
-    return RR_OK;
-  });
-}
-
-template <typename T>
-int launch_tiled(const rr_igemm_desc *d, IgemmArgs &a, const ConvRoute &r, hipStream_t st) {
-  if (r.tile_bc == 128) return launch_mode<T, 128, 128, 2>(d, a, st);
-  if (r.tile_bp == 256) return launch_mode<T, 64, 256, 1>(d, a, st);
-  return launch_mode<T, 64, 128, 2>(d, a, st);
+  hipLaunchKernelGGL((igemm3_halo_kernel<BC, W, RR_CONV3X3, BP, NT>), grid, block, 0, st, a);
+  RR_CHECK_LAUNCH();
+  return RR_OK;
 }
 
 // the LDS-halo or the tiled kernel of route r
 int dispatch(const rr_igemm_desc *d, IgemmArgs &a, const ConvRoute &r, hipStream_t st) {
   if (r.family == CF_HALO) {
-    if (r.halo_bc == 128) return launch_halo<128, 256>(d, a, st);
-    if (r.halo_bc == 64) return launch_halo<64, 256>(d, a, st);
-    return launch_halo<16, 256>(d, a, st);
+#define HALO_GO(BC, W) if (r.halo_bc == BC && d->w == W) return launch_halo<BC, W>(a, st);
+    HALO_LIST(HALO_GO)
+#undef HALO_GO
+    return RR_EUNSUPPORTED;
   }
-  return rr_dispatch_elt(d->dtype, [&](auto tag) { return launch_tiled<typename decltype(tag)::type>(d, a, r, st); });
+  return rr_dispatch_elt(d->dtype, [&](auto tag) {
+#define TILE_GO(BC, BP, WC) \
+  if (r.tile_bc == BC && r.tile_bp == BP) return launch_mode<typename decltype(tag)::type, BC, BP, WC>(d, a, st);
+    TILE_LIST(TILE_GO)
+#undef TILE_GO
+    return (int)RR_EUNSUPPORTED;
+  });
 }
 
 const char *halo_name(int hb, int w) {
-#define HN(bc) {"igemm3_halo_kernel<" #bc ",8>", "igemm3_halo_kernel<" #bc ",16>", "igemm3_halo_kernel<" #bc ",32>", "igemm3_halo_kernel<" #bc ",64>"}
-  static const char *const names[3][4] = {HN(16), HN(64), HN(128)};
-#undef HN
-  return names[hb == 16 ? 0 : hb == 64 ? 1 : 2][w == 8 ? 0 : w == 16 ? 1 : w == 32 ? 2 : 3];
+#define HALO_NAME(BC, W) if (hb == BC && w == W) return "igemm3_halo_kernel<" #BC "," #W ">";
+  HALO_LIST(HALO_NAME)
+#undef HALO_NAME
+  return "unsupported";
 }
 
 const char *tiled_name(const rr_igemm_desc *d, Tile t) {
+  if (!rr_dtype_ok(d->dtype) || d->mode < 0 || d->mode > 3) return "unsupported";
 #define TN(ty, tl) {"igemm_kernel<" ty "," tl ",m0>", "igemm_kernel<" ty "," tl ",m1>", "igemm_kernel<" ty "," tl ",m2>", "igemm_kernel<" ty "," tl ",m3>"}
-  static const char *const tn[2][3][4] = {{TN("f32", "128,128"), TN("f32", "64,256"), TN("f32", "64,128")},
-                                          {TN("bf16", "128,128"), TN("bf16", "64,256"), TN("bf16", "64,128")}};
+#define TILE_NAME(BC, BP, WC)                                                                    \
+  static const char *const tn##BC##BP[2][4] = {TN("f32", #BC "," #BP), TN("bf16", #BC "," #BP)}; \
+  if (t.bc == BC && t.bp == BP) return tn##BC##BP[d->dtype == RR_BF16][d->mode];
+  TILE_LIST(TILE_NAME)
+#undef TILE_NAME
 #undef TN
-  const int ti = t.bc == 128 ? 0 : (t.bp == 256 ? 1 : 2);
-  const int mi = d->mode >= 0 && d->mode <= 3 ? d->mode : 0;
-  return tn[d->dtype == RR_BF16][ti][mi];
+  return "unsupported";
 }
 
 // the descriptors rr_igemm_pool, rr_igemm_dgrad_sc and rr_igemm_pre are for

@@ -863,109 +863,87 @@ __global__ __launch_bounds__(512, 2) void stream3_kernel(S3Args a, int nsteps) {
   }
 }
 
+// The instantiated kernels, one entry per instance family: (flag set, MP,
+// late-epilogue stagger, whole-row instances at W = 64 and 32?, 32-wide column
+// strip instance?).  The acceptance tests (s3_has), the launch (s3_go) and so
+// the pick are generated from this list: a flag set is eligible exactly where
+// it is instantiated.  MP: 128-pixel steps (2) except the bias-only and
+// ReLU-only forwards, which keep 256-pixel steps (4) with the stagger -- it
+// measured faster only there (it keeps acc live across the loop back-edge:
+// the statistics variants spill with it).
+// - the dgrad (no epilogue) and the bias + ReLU forward in 128-pixel steps:
+//   in the graph-captured step they beat the staggered 256-pixel form by
+//   0.8 % (profiles/r3an_ab_s3_mp4.txt; the stagger had been measured faster
+//   on eager launches)
+// - the BN-statistics forward in 128-pixel steps: with 256-pixel steps the
+//   statistics registers pushed the kernel past 256 VGPRs (10 spilled at
+//   W = 64, 26 at W = 32: scratch traffic in the step loop, 224 us vs 139 us
+//   for the non-statistics 64x64 forward); 128-pixel steps fit in 220 (graph
+//   step +1.3 %, profiles/r3am_ab_s3_stats.txt)
+// - the pool with its window index (rr_igemm_pool) and the 1x1 second source
+//   (rr_igemm_dgrad_sc): the bias + ReLU forward's and the plain dgrad's form
+//   (256-pixel steps at W = 64 were bitwise equal and within the run order's
+//   noise, profiles/r5zi_pool_bench.jsonl, r5zj_pool_bench.jsonl)
+// - column strips: the plain conv / dgrad, bias (+ ReLU), and the BN-folded
+//   eval epilogues of the reference's 224 pipeline (17:84-86, 18:46-47), all
+//   in 128-pixel steps (4 rows) without stagger; the training epilogues
+//   (statistics, operands, BN backward, the window index) stay on the
+//   tap-reuse conv there
+#define S3_LIST(X)                                                                   \
+  X(0, 2, 0, true, true)                                                             \
+  X(F_BIAS | F_RELU, 2, 0, true, true)                                               \
+  X(F_BIAS, 4, 1, true, false)                                                       \
+  X(F_BIAS, 2, 0, false, true)                                                       \
+  X(F_STATS, 2, 0, true, false)                                                      \
+  X(F_BIAS | F_STATS, 2, 0, true, false)                                             \
+  X(F_RELU, 4, 1, true, false)                                                       \
+  X(F_ACC, 2, 0, true, false)                                                        \
+  X(F_MASK, 2, 0, true, false)                                                       \
+  X(F_ACC | F_MASK, 2, 0, true, false)                                               \
+  X(F_BNBWD, 2, 0, true, false)                                                      \
+  X(F_BIAS | F_STATS | F_PRE, 2, 0, true, false)                                     \
+  /* the eval epilogues (rr_igemm_ex) */                                             \
+  X(F_BIAS | F_PRELU, 2, 0, true, true)                                              \
+  X(F_BIAS | F_RES | F_RELU, 2, 0, true, true)                                       \
+  X(F_BIAS | F_RES | F_RELU | F_POOL | F_PFULL | F_PNOIDX, 2, 0, true, true)         \
+  X(F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX, 2, 0, true, true)                 \
+  X(F_BIAS | F_RELU | F_POOL | F_PNOIDX, 2, 0, true, true)                           \
+  X(F_BIAS | F_RELU | F_POOL, 2, 0, true, false)                                     \
+  X(F_RELU | F_POOL, 2, 0, true, false)                                              \
+  X(F_SC, 2, 0, true, false)
+
+// is flag set f instantiated for whole rows / for column strips?
+bool s3_has(int f, bool strip) {
+#define S3_HAS(F, MP, STG, WHOLE, STRIP) if (f == (F) && (strip ? STRIP : WHOLE)) return true;
+  S3_LIST(S3_HAS)
+#undef S3_HAS
+  return false;
+}
+
 // epilogue flag set of a plain call, or -1 when the streaming kernel has no
-// instance for it (the tiled kernel takes the call)
+// whole-row instance for it (the tiled kernel takes the call)
 int s3_flags(const rr_igemm_desc *d) {
   const int f = (d->has_bias ? F_BIAS : 0) | (d->want_stats ? F_STATS : 0) |
                 (d->act == RR_ACT_RELU ? F_RELU : 0) | (d->accumulate ? F_ACC : 0) |
                 (d->has_mask ? F_MASK : 0);
-  switch (f) {
-    case 0: case F_BIAS: case F_STATS: case F_BIAS | F_STATS: case F_RELU: case F_BIAS | F_RELU:
-    case F_ACC: case F_MASK: case F_ACC | F_MASK:
-      return f;
-    default:
-      return -1;
-  }
+  return s3_has(f, false) ? f : -1;
 }
 
-template <int W, int MP, int F, int STG = -1, bool SM = false>
-void launch1(const S3Args &a, int P, hipStream_t st) {
-  // the late-epilogue stagger measured faster only for 256-pixel steps
-  // without the BN-statistics registers (it keeps acc live across the loop
-  // back-edge: the stats variants spill with it)
-  constexpr int STAG = STG >= 0 ? STG : ((MP == 4 && !(F & F_STATS)) ? 1 : 0);
-  hipLaunchKernelGGL((stream3_kernel<W, MP, F, STAG, SM>), dim3(S3_WG), dim3(512), 0, st, a, P / (64 * MP));
-}
-
-template <int W>
-int launch_w(const S3Args &a, int f, int P, hipStream_t st) {
-  // the dgrad (no epilogue) and the bias + ReLU forward in 128-pixel steps
-  // too: in the graph-captured step they beat the staggered 256-pixel form
-  // by 0.8 % (profiles/r3an_ab_s3_mp4.txt; the stagger had been measured
-  // faster on eager launches)
-  switch (f) {
-    case 0: launch1<W, 2, 0, 0>(a, P, st); break;
-    case F_BIAS | F_RELU: launch1<W, 2, F_BIAS | F_RELU, 0>(a, P, st); break;
-    case F_BIAS: launch1<W, 4, F_BIAS>(a, P, st); break;
-    // the BN-statistics forward in 128-pixel steps: with 256-pixel steps the
-    // statistics registers pushed the kernel past 256 VGPRs (10 spilled at
-    // W = 64, 26 at W = 32: scratch traffic in the step loop, 224 us vs 139
-    // us for the non-statistics 64x64 forward); 128-pixel steps fit in 220
-    // (graph step +1.3 %, profiles/r3am_ab_s3_stats.txt)
-    case F_STATS: launch1<W, 2, F_STATS, 0>(a, P, st); break;
-    case F_BIAS | F_STATS: launch1<W, 2, F_BIAS | F_STATS, 0>(a, P, st); break;
-    case F_RELU: launch1<W, 4, F_RELU>(a, P, st); break;
-    case F_ACC: launch1<W, 2, F_ACC>(a, P, st); break;
-    case F_MASK: launch1<W, 2, F_MASK>(a, P, st); break;
-    case F_ACC | F_MASK: launch1<W, 2, F_ACC | F_MASK>(a, P, st); break;
-    case F_BNBWD: launch1<W, 2, F_BNBWD>(a, P, st); break;
-    case F_BIAS | F_STATS | F_PRE: launch1<W, 2, F_BIAS | F_STATS | F_PRE, 0>(a, P, st); break;
-    // the eval epilogues (rr_igemm_ex), 128-pixel steps
-    case F_BIAS | F_PRELU: launch1<W, 2, F_BIAS | F_PRELU, 0>(a, P, st); break;
-    case F_BIAS | F_RES | F_RELU: launch1<W, 2, F_BIAS | F_RES | F_RELU, 0>(a, P, st); break;
-    case F_BIAS | F_RES | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
-      launch1<W, 2, F_BIAS | F_RES | F_RELU | F_POOL | F_PFULL | F_PNOIDX, 0>(a, P, st); break;
-    case F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
-      launch1<W, 2, F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX, 0>(a, P, st); break;
-    case F_BIAS | F_RELU | F_POOL | F_PNOIDX: launch1<W, 2, F_BIAS | F_RELU | F_POOL | F_PNOIDX, 0>(a, P, st); break;
-    // the pool with its window index (rr_igemm_pool) and the 1x1 second
-    // source (rr_igemm_dgrad_sc): 128-pixel steps, no stagger -- the bias +
-    // ReLU forward's and the plain dgrad's form (256-pixel steps at W = 64
-    // were bitwise equal and within the run order's noise,
-    // profiles/r5zi_pool_bench.jsonl, r5zj_pool_bench.jsonl)
-    case F_BIAS | F_RELU | F_POOL: launch1<W, 2, F_BIAS | F_RELU | F_POOL, 0>(a, P, st); break;
-    case F_RELU | F_POOL: launch1<W, 2, F_RELU | F_POOL, 0>(a, P, st); break;
-    case F_SC: launch1<W, 2, F_SC, 0>(a, P, st); break;
-    default: return RR_EUNSUPPORTED;
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
-}
-
-// column-strip mode: the flag sets it has instances for -- the plain conv /
-// dgrad, bias (+ ReLU), and the BN-folded eval epilogues of the reference's
-// 224 pipeline (17:84-86, 18:46-47); the training epilogues (statistics,
-// operands, BN backward, the window index) stay on the tap-reuse conv there
-bool s3_strip_flags(int f) {
-  switch (f) {
-    case 0: case F_BIAS: case F_BIAS | F_RELU: case F_BIAS | F_PRELU: case F_BIAS | F_RES | F_RELU:
-    case F_BIAS | F_RES | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
-    case F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
-    case F_BIAS | F_RELU | F_POOL | F_PNOIDX:
-      return true;
-    default:
-      return false;
-  }
-}
-
-int launch_strips(const S3Args &a, int f, int P, hipStream_t st) {
-  // 32-wide strips, 128-pixel steps (4 rows), no stagger
-  switch (f) {
-    case 0: launch1<32, 2, 0, 0, true>(a, P, st); break;
-    case F_BIAS: launch1<32, 2, F_BIAS, 0, true>(a, P, st); break;
-    case F_BIAS | F_RELU: launch1<32, 2, F_BIAS | F_RELU, 0, true>(a, P, st); break;
-    case F_BIAS | F_PRELU: launch1<32, 2, F_BIAS | F_PRELU, 0, true>(a, P, st); break;
-    case F_BIAS | F_RES | F_RELU: launch1<32, 2, F_BIAS | F_RES | F_RELU, 0, true>(a, P, st); break;
-    case F_BIAS | F_RES | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
-      launch1<32, 2, F_BIAS | F_RES | F_RELU | F_POOL | F_PFULL | F_PNOIDX, 0, true>(a, P, st); break;
-    case F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX:
-      launch1<32, 2, F_BIAS | F_RELU | F_POOL | F_PFULL | F_PNOIDX, 0, true>(a, P, st); break;
-    case F_BIAS | F_RELU | F_POOL | F_PNOIDX:
-      launch1<32, 2, F_BIAS | F_RELU | F_POOL | F_PNOIDX, 0, true>(a, P, st); break;
-    default: return RR_EUNSUPPORTED;
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+// the launch of flag set f: whole rows of W = 64 / 32 (SM = false), or
+// 32-wide strips (W = 32, SM = true)
+template <int W, bool SM>
+int s3_go(const S3Args &a, int f, int P, hipStream_t st) {
+#define S3_GO(F, MP, STG, WHOLE, STRIP)                                                              \
+  if constexpr (SM ? STRIP : WHOLE)                                                                  \
+    if (f == (F)) {                                                                                  \
+      hipLaunchKernelGGL((stream3_kernel<W, MP, (F), STG, SM>), dim3(S3_WG), dim3(512), 0, st, a,    \
+                         P / (64 * MP));                                                             \
+      RR_CHECK_LAUNCH();                                                                             \
+      return RR_OK;                                                                                  \
+    }
+  S3_LIST(S3_GO)
+#undef S3_GO
+  return RR_EUNSUPPORTED;
 }
 
 // column width of the streaming kernel on a w-wide map: the whole row at w =
@@ -1030,15 +1008,18 @@ S3Pick stream3_pick(const rr_igemm_desc *d, const RrPath &p, int kind) {
   if (!cw || d->c_in2) return no;
   const int strip = cw != d->w;
   const int f = kind == CK_BNBWD ? F_BNBWD : kind == CK_EX ? s3_ex_flags(d) : s3_flags(d);
-  if (f < 0 || (strip && !s3_strip_flags(f))) return no;
+  if (f < 0 || !s3_has(f, strip)) return no;
+  S3Pick k = {f, strip};
   switch (kind) {
     case CK_POOL:   // (the eval judge: no window index)
-      return d->has_bias ? S3Pick{F_BIAS | F_RELU | F_POOL | F_PNOIDX, strip} : no;
-    case CK_POOL_IDX: return strip ? no : S3Pick{f | F_POOL, 0};
-    case CK_DGRAD_SC: return strip || f != 0 ? no : S3Pick{F_SC, 0};
-    case CK_PRE: return strip || f != (F_BIAS | F_STATS) ? no : S3Pick{f | F_PRE, 0};
-    default: return S3Pick{f, strip};
+      k = d->has_bias ? S3Pick{F_BIAS | F_RELU | F_POOL | F_PNOIDX, strip} : no; break;
+    case CK_POOL_IDX: k = strip ? no : S3Pick{f | F_POOL, 0}; break;
+    case CK_DGRAD_SC: k = strip || f != 0 ? no : S3Pick{F_SC, 0}; break;
+    case CK_PRE: k = strip || f != (F_BIAS | F_STATS) ? no : S3Pick{f | F_PRE, 0}; break;
+    default: break;
   }
+  // (the kind's flag set has an instance in the mode it is launched in)
+  return k.flags >= 0 && s3_has(k.flags, k.strip != 0) ? k : no;
 }
 
 // workgroups (= rows of the stats / bnbwd partial slabs): fixed, so the count
@@ -1057,9 +1038,9 @@ const char *stream3_name(const rr_igemm_desc *d, S3Pick k, int kind) {
 int stream3_launch(const rr_igemm_desc *d, S3Args a, S3Pick k, hipStream_t st) {
   a.wld = 64; a.woff = 0; a.w = d->w;
   const int P = d->n * d->h * d->w;
-  if (k.strip) return launch_strips(a, k.flags, P, st);
-  if (d->w == 64) return launch_w<64>(a, k.flags, P, st);
-  return launch_w<32>(a, k.flags, P, st);
+  if (k.strip) return s3_go<32, true>(a, k.flags, P, st);
+  if (d->w == 64) return s3_go<64, false>(a, k.flags, P, st);
+  return s3_go<32, false>(a, k.flags, P, st);
 }
 
 #ifdef RR_S3_STAMPS

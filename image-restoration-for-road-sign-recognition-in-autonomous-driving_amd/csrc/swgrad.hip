@@ -406,13 +406,12 @@ int swgrad_launch(const rr_wgrad_desc *d, const void *dy, const void *x1, const 
   a.nsteps = (int)((long long)d->n * d->h * d->w / 128);
   a.pre_s = pre_s; a.pre_b = pre_b; a.pre_alpha = pre_alpha;
   const dim3 grid(a.nwg_ps * S), block(512);
-  if (pre_s) {
-    if (d->w == 64) hipLaunchKernelGGL((swgrad_kernel<64, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((swgrad_kernel<32, true>), grid, block, 0, st, a);
-  } else {
-    if (d->w == 64) hipLaunchKernelGGL((swgrad_kernel<64, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((swgrad_kernel<32, false>), grid, block, 0, st, a);
-  }
-  RR_CHECK_LAUNCH();
-  return RR_OK;
+  auto go = [&](auto pre) {
+    return rr_dispatch_int<64, 32>(d->w, [&](auto w) {   // swgrad_ok: one of these
+      hipLaunchKernelGGL((swgrad_kernel<decltype(w)::value, decltype(pre)::value>), grid, block, 0, st, a);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
+  };
+  return pre_s ? go(std::true_type{}) : go(std::false_type{});
 }

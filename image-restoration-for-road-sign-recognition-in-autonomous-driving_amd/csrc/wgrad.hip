@@ -692,12 +692,38 @@ int launch(const rr_wgrad_desc *d, const Plan &pl, WgradArgs &a, hipStream_t st)
   });
 }
 
+// The instantiated tiled kernels: (BA, BB), each for both dtypes and the
+// three modes; and the LDS-halo kernel's map widths.  The launch and the name
+// of a route read these lists: a value outside them is RR_EUNSUPPORTED /
+// "unsupported".
+#define WG_TILE_LIST(X) X(128, 128) X(128, 64) X(64, 128) X(64, 64)
+#define WG_HALO_LIST(X) X(64) X(32) X(16) X(8)
+
 template <typename T>
 int launch_t(const rr_wgrad_desc *d, const Plan &pl, WgradArgs &a, hipStream_t st) {
-  if (pl.BA == 128 && pl.BB == 128) return launch<T, 128, 128>(d, pl, a, st);
-  if (pl.BA == 128) return launch<T, 128, 64>(d, pl, a, st);
-  if (pl.BB == 128) return launch<T, 64, 128>(d, pl, a, st);
-  return launch<T, 64, 64>(d, pl, a, st);
+#define WG_TILE_GO(BA_, BB_) if (pl.BA == BA_ && pl.BB == BB_) return launch<T, BA_, BB_>(d, pl, a, st);
+  WG_TILE_LIST(WG_TILE_GO)
+#undef WG_TILE_GO
+  return RR_EUNSUPPORTED;
+}
+
+const char *tiled_name(const rr_wgrad_desc *d, const Plan &pl) {
+  if (!rr_dtype_ok(d->dtype) || d->mode < 0 || d->mode > 3) return "unsupported";
+#define TN(ty, tl) {"wgrad_kernel<" ty "," tl ",m0>", "wgrad_kernel<" ty "," tl ",m1>", "wgrad_kernel<" ty "," tl ",m2>", "wgrad_kernel<" ty "," tl ",m3>"}
+#define WG_TILE_NAME(BA_, BB_)                                                                         \
+  static const char *const tn##BA_##BB_[2][4] = {TN("f32", #BA_ "," #BB_), TN("bf16", #BA_ "," #BB_)}; \
+  if (pl.BA == BA_ && pl.BB == BB_) return tn##BA_##BB_[d->dtype == RR_BF16][d->mode];
+  WG_TILE_LIST(WG_TILE_NAME)
+#undef WG_TILE_NAME
+#undef TN
+  return "unsupported";
+}
+
+const char *halo_name(int w) {
+#define WG_HALO_NAME(W) if (w == W) return "wgrad3_halo_kernel<" #W ">";
+  WG_HALO_LIST(WG_HALO_NAME)
+#undef WG_HALO_NAME
+  return "unsupported";
 }
 
 }  // namespace
@@ -755,19 +781,12 @@ static WgradRoute wgrad_route(const rr_wgrad_desc *d, const RrPath &p) {
     r.family = WF_HALO;
     r.halo = halo_plan(d);
     r.nsplit = r.halo.nsplit;
-    r.name = d->w == 64 ? "wgrad3_halo_kernel<64>" : d->w == 32 ? "wgrad3_halo_kernel<32>"
-             : d->w == 16 ? "wgrad3_halo_kernel<16>" : "wgrad3_halo_kernel<8>";
+    r.name = halo_name(d->w);
   } else {
     r.family = WF_TILED;
     r.plan = plan_of(d);
     r.CA = r.plan.CA; r.CB = r.plan.CB; r.taps = r.plan.taps; r.nsplit = r.plan.nsplit;
-#define TN(ty, tl) {"wgrad_kernel<" ty "," tl ",m0>", "wgrad_kernel<" ty "," tl ",m1>", "wgrad_kernel<" ty "," tl ",m2>", "wgrad_kernel<" ty "," tl ",m3>"}
-    static const char *const tn[2][2][2][4] = {
-        {{TN("f32", "64,64"), TN("f32", "64,128")}, {TN("f32", "128,64"), TN("f32", "128,128")}},
-        {{TN("bf16", "64,64"), TN("bf16", "64,128")}, {TN("bf16", "128,64"), TN("bf16", "128,128")}}};
-#undef TN
-    const int mi = d->mode >= 0 && d->mode <= 3 ? d->mode : 0;
-    r.name = tn[d->dtype == RR_BF16][r.plan.BA == 128][r.plan.BB == 128][mi];
+    r.name = tiled_name(d, r.plan);
   }
   r.alayout = r.family != WF_SWGRAD && r.CA % 4 == 0;
   r.ws_bytes = (size_t)r.nsplit * r.CA * r.taps * r.CB * sizeof(float);
@@ -817,11 +836,15 @@ static int wgrad_partial(const rr_wgrad_desc *d, const WgradRoute &r, const void
     ha.nablk = ha.CA / 64; ha.nbblk = ha.CB / 64;
     ha.xcd = 1;                                  // XCD-aware workgroup order
     const dim3 grid((unsigned)(ha.nablk * ha.nbblk * r.nsplit)), block(256);
-    return rr_dispatch_int<64, 32, 16, 8>(d->w, [&](auto w) {   // halo_ok: one of these
-      hipLaunchKernelGGL((wgrad3_halo_kernel<decltype(w)::value>), grid, block, 0, st, ha);
-      RR_CHECK_LAUNCH();
-      return RR_OK;
-    });
+#define WG_HALO_GO(W)                                                       \
+  if (d->w == W) {                                                          \
+    hipLaunchKernelGGL((wgrad3_halo_kernel<W>), grid, block, 0, st, ha);    \
+    RR_CHECK_LAUNCH();                                                      \
+    return RR_OK;                                                           \
+  }
+    WG_HALO_LIST(WG_HALO_GO)
+#undef WG_HALO_GO
+    return RR_EUNSUPPORTED;
   }
   const Plan &pl = r.plan;
   WgradArgs a;
