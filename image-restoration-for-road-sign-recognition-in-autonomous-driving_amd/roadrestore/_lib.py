@@ -70,6 +70,32 @@ class RaggedImage(C.Structure):             # mirrors rr_ragged_image
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class PngImage(C.Structure):                # mirrors rr_png_image
+    _fields_ = [("src", C.c_int64), ("dst", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("channels", C.c_int32), ("kind", C.c_int32)]
+
+
+class PngInfo(C.Structure):                 # mirrors rr_png_info
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32),
+                ("status", C.c_int32), ("reason", C.c_int32)]
+
+
+# rr_png_reason -> the words read_png's ValueError uses
+PNG_REASON = {
+    1: "cannot open or read the file",
+    2: "not a PNG file (bad signature)",
+    3: "truncated file",
+    4: "chunk CRC mismatch",
+    5: "malformed IHDR",
+    6: "unsupported kind of PNG (only 8-bit grey, grey+alpha, RGB and RGBA without interlace are read)",
+    7: "bad chunk framing or order",
+    8: "incomplete or corrupt zlib stream in IDAT",
+    9: "wrong inflated size (IDAT does not hold h * (1 + w * channels) bytes)",
+    10: "filter byte above 4",
+    11: "record does not match the file or leaves the buffer",
+}
+
+
 class BnFinalizeDesc(C.Structure):          # mirrors rr_bn_finalize_desc
     _fields_ = [("C", C.c_int32), ("blocks", C.c_int32), ("count", C.c_int64),
                 ("part", C.c_void_p), ("bias", C.c_void_p), ("gamma", C.c_void_p),
@@ -187,6 +213,10 @@ _SIGS = {
     "rr_ragged_check": (I_, [I_, I_, S_, P_, I_, I_, I_, I_]),
     "rr_resize_ragged_workspace": (S_, [I_, I_, I_, I_, I_, I_]),
     "rr_resize_ragged_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, S_, P_, I_, P_, P_, P_, P_, S_, P_]),
+    "rr_png_probe": (I_, [I_, P_, P_, I_]),
+    "rr_png_inflate": (I_, [I_, P_, P_, P_, S_, P_, I_]),
+    "rr_png_table_check": (I_, [I_, S_, S_, P_, I_, I_]),
+    "rr_png_unfilter": (I_, [I_, I_, I_, P_, S_, P_, P_, S_, P_]),
     "rr_ssim_workspace": (S_, [I_, I_]),
     "rr_ssim_u8": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, S_, P_]),
     "rr_distort_workspace": (S_, [I_, I_, I_, I_]),

@@ -22,6 +22,10 @@ DataLoader workers and in the inference loop).  Here they take a whole
   the reference resizes each on its own (05:24-32, 14:68, 18:28-36).  A
   ``RaggedBatch`` holds n images of unequal size in one device buffer;
   ``Resize`` / ``Compose`` turn it into the dense batch in two launches.
+* ``read_png`` / ``read_images`` -- the PNG files of 17:69-79, 18:35,
+  07:52-66 and the mixed ``.ppm`` + ``.png`` list of 08:84-88 into the same
+  ``RaggedBatch``: inflate on host threads, the row filters undone and
+  ``convert('RGB')`` applied on the device for the whole batch in one launch.
 """
 from __future__ import annotations
 
@@ -35,14 +39,14 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import (RR_DISTORT_BLUR, RR_DISTORT_FOG, RR_DISTORT_KMAX, RR_DISTORT_NOISE,
-                   DistortParam, RaggedImage, lib)
+from ._lib import (PNG_REASON, RR_DISTORT_BLUR, RR_DISTORT_FOG, RR_DISTORT_KMAX, RR_DISTORT_NOISE,
+                   RR_EUNSUPPORTED, DistortParam, PngImage, PngInfo, RaggedImage, lib)
 
 __all__ = ["Resize", "ToTensor", "Normalize", "Compose", "apply_random_distortions",
            "encode_png", "write_png",
            "RandomDistortion", "motion_blur_table",
            "apply_compound_distortion", "distortion_params", "psnr", "ssim", "cv_resize",
-           "RaggedBatch", "read_ppm", "ImageFolder", "find_images",
+           "RaggedBatch", "read_ppm", "read_png", "read_images", "ImageFolder", "find_images",
            "IMAGENET_MEAN", "IMAGENET_STD"]
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)      # 18:31
@@ -313,6 +317,142 @@ def read_ppm(paths, device, threads=0):
     return RaggedBatch(host[:max(total, 1)].to(device, non_blocking=True), rec, 3)
 
 
+# ---------------------------------------------------------------------------
+# PNG input (17:69-79, 18:35, 07:52-66, 08:84-88): host inflate, device unfilter
+
+_PNG_RECORD = np.dtype([("src", "<i8"), ("dst", "<i8"), ("h", "<i4"), ("w", "<i4"),
+                        ("channels", "<i4"), ("kind", "<i4")])                  # rr_png_image
+_PNG_INFO = np.dtype([("h", "<i4"), ("w", "<i4"), ("channels", "<i4"), ("status", "<i4"),
+                      ("reason", "<i4")])                                       # rr_png_info
+assert _PNG_RECORD.itemsize == C.sizeof(PngImage) == 32
+assert _PNG_INFO.itemsize == C.sizeof(PngInfo) == 20
+
+
+def _png_raise(paths, info):
+    """ValueError naming the first file rr_png_probe / rr_png_inflate refused"""
+    for p, st, why in zip(paths, info["status"], info["reason"]):
+        if st != 0:
+            raise ValueError(f"{p}: {PNG_REASON.get(int(why), f'reason {int(why)}')} "
+                             f"({'unsupported' if st == RR_EUNSUPPORTED else 'invalid'} PNG)")
+
+
+def _stage_files(paths, is_png, device, threads):
+    """The host half of ``_read_files``: probe, one host buffer (PNG: the
+    inflated scanlines, PPM: the file) with the rr_png_image table behind it
+    at a 16-byte boundary -> (host buffer, records, data bytes, table offset,
+    output bytes, (max_h, max_w)).  Raises ValueError for a bad file."""
+    n = len(paths)
+    L = lib()
+    workers = int(threads) if threads else min(8, n)
+    rec = np.zeros(n, dtype=_PNG_RECORD)
+    png = [i for i in range(n) if is_png[i]]
+    ppm = [i for i in range(n) if not is_png[i]]
+    slot = np.zeros(n, dtype=np.int64)
+    if png:
+        sub = (C.c_char_p * len(png))(*[os.fsencode(paths[i]) for i in png])
+        info = np.zeros(len(png), dtype=_PNG_INFO)
+        L.rr_png_probe(len(png), C.cast(sub, C.c_void_p), info.ctypes.data, workers)
+        _png_raise([paths[i] for i in png], info)
+        rec["h"][png], rec["w"][png], rec["channels"][png] = info["h"], info["w"], info["channels"]
+        rec["kind"][png] = 1
+        slot[png] = info["h"].astype(np.int64) * (1 + info["w"].astype(np.int64) * info["channels"])
+    for i in ppm:
+        slot[i] = os.path.getsize(paths[i])
+        rec["channels"][i] = 3
+    start = np.cumsum(slot) - slot
+    data_bytes = int(slot.sum())
+    table_off = (data_bytes + 15) & ~15
+    host = _host_buffer(table_off + 32 * n, device)
+    buf = host.numpy()
+    rec["src"] = start
+
+    def one_ppm(i):
+        a, b = int(start[i]), int(start[i] + slot[i])
+        with open(paths[i], "rb") as f:
+            got = f.readinto(memoryview(buf[a:b])) if b > a else 0
+        w, h, maxval, off = _ppm_header(bytes(buf[a:a + min(got, _PPM_HEAD)]), paths[i])
+        if not 1 <= maxval <= 255:
+            raise ValueError(f"{paths[i]}: maxval {maxval}: only 8-bit PPM (maxval <= 255) is read")
+        if h < 1 or w < 1 or h > 2 ** 31 - 1 or w > 2 ** 31 - 1:
+            raise ValueError(f"{paths[i]}: bad PPM size {w} x {h}")
+        if off + h * w * 3 > got:
+            raise ValueError(f"{paths[i]}: truncated PPM: {w} x {h} needs {h * w * 3} pixel bytes, "
+                             f"{max(got - off, 0)} present")
+        rec[i] = (a + off, 0, h, w, 3, 0)
+
+    if workers <= 1 or len(ppm) <= 1:
+        for i in ppm:
+            one_ppm(i)
+    else:
+        with ThreadPoolExecutor(workers) as pool:
+            list(pool.map(one_ppm, ppm))
+    if png:
+        arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+        info = np.zeros(n, dtype=_PNG_INFO)
+        L.rr_png_inflate(n, C.cast(arr, C.c_void_p), rec.ctypes.data, host.data_ptr(), data_bytes,
+                         info.ctypes.data, workers)
+        _png_raise(paths, info)
+    nb = rec["h"].astype(np.int64) * rec["w"] * 3
+    rec["dst"] = np.cumsum(nb) - nb
+    out_bytes = int(nb.sum())
+    max_hw = (int(rec["h"].max()), int(rec["w"].max()))
+    rc = L.rr_png_table_check(n, data_bytes, out_bytes, rec.ctypes.data, max_hw[0], max_hw[1])
+    if rc != 0:
+        raise ValueError(f"read_png: table rejected by rr_png_table_check ({rc}): sizes up to {max_hw}"
+                         + (" (widths above 8192 are not read)" if rc == RR_EUNSUPPORTED else ""))
+    buf[table_off:table_off + 32 * n] = rec.view(np.uint8)
+    return host, rec, data_bytes, table_off, out_bytes, max_hw
+
+
+def _read_files(paths, is_png, device, threads):
+    """PNG and binary-PPM files, in the order of ``paths``, -> RaggedBatch of
+    RGB images on ``device``: the host stage, one H2D copy of buffer and
+    table, one launch (ops.png_unfilter)."""
+    n = len(paths)
+    host, rec, data_bytes, table_off, out_bytes, max_hw = _stage_files(paths, is_png, device, threads)
+    dev = host.to(device, non_blocking=True)
+    out = ops.png_unfilter(dev[:data_bytes], dev[table_off:table_off + 32 * n].view(n, 32), max_hw,
+                           out_bytes)
+    images = np.zeros(n, dtype=_RECORD)
+    images["offset"], images["h"], images["w"] = rec["dst"], rec["h"], rec["w"]
+    return RaggedBatch(out, images, 3)
+
+
+def read_png(paths, device, threads=0):
+    """PNG files (8-bit grey, grey + alpha, RGB or RGBA, no interlace: what
+    cv2.imwrite / PIL save and imgproc.write_png writes) -> RaggedBatch of RGB
+    images on ``device``, each as ``Image.open(p).convert('RGB')`` gives it
+    (17:69-79, 18:35, 07:52-66): grey replicated, alpha dropped.  The host
+    probes the headers, inflates every file's IDAT stream on ``threads``
+    threads (0 = up to 8) into one pinned buffer and copies it with the record
+    table in one non-blocking H2D copy; the row filters are undone on the
+    device for the whole batch in one launch.  A file that is not such a PNG
+    (palette, 16-bit, interlaced, bad CRC, truncated, wrong inflated size, bad
+    filter byte) raises ``ValueError`` naming it and the reason before
+    anything is launched.  No CPU path: ``device="cpu"`` raises."""
+    paths = [os.fspath(p) for p in paths]
+    if not paths:
+        raise ValueError("read_png: no paths")
+    return _read_files(paths, [True] * len(paths), device, threads)
+
+
+def read_images(paths, device, threads=0):
+    """Image files by extension -> one RaggedBatch in the order of ``paths``:
+    all ``.ppm`` -> ``read_ppm`` (unchanged, zero-copy); all ``.png`` ->
+    ``read_png``; a mixed list (08:84-88) -> one buffer, one table of PNG and
+    raw records, one launch."""
+    paths = [os.fspath(p) for p in paths]
+    if not paths:
+        raise ValueError("read_images: no paths")
+    ext = [os.path.splitext(p)[1].lower() for p in paths]
+    for p, e in zip(paths, ext):
+        if e not in (".ppm", ".png"):
+            raise ValueError(f"{p}: only .ppm and .png files are read")
+    if all(e == ".ppm" for e in ext):
+        return read_ppm(paths, device, threads)
+    return _read_files(paths, [e == ".png" for e in ext], device, threads)
+
+
 def find_images(root, pattern="*/*.ppm"):
     """``sorted(Path(root).glob(pattern))``: the file list of 14:68"""
     return sorted(Path(root).glob(pattern))
@@ -325,7 +465,9 @@ class ImageFolder:
     class order and, within a class, in ``sorted(os.walk(dir))`` order with
     each directory's file names sorted; the extension match ignores case.  A
     class without files keeps its index (torchvision's ``find_classes`` counts
-    it too) and contributes no samples.
+    it too) and contributes no samples.  ``extensions``: ``(".ppm",)`` by
+    default; ``(".png",)`` or ``(".ppm", ".png")`` list PNG files too (18:35
+    over the directory 17:89-99 wrote) and load them through ``read_images``.
 
     ``load(indices, device)`` -> (RaggedBatch, int64 labels on ``device``);
     ``batches(batch_size, shuffle, generator)`` yields that for one pass over
@@ -356,7 +498,7 @@ class ImageFolder:
     def load(self, indices, device=None):
         device = self.device if device is None else torch.device(device)
         indices = [int(i) for i in indices]
-        batch = read_ppm([self.samples[i][0] for i in indices], device, self.threads)
+        batch = read_images([self.samples[i][0] for i in indices], device, self.threads)
         labels = torch.tensor([self.samples[i][1] for i in indices], dtype=torch.int64)
         if device.type == "cuda":
             labels = labels.pin_memory()

@@ -25,7 +25,7 @@ __all__ = [
     "motion_blur_kernel", "first_conv_wgrad_act", "affine_act_pool", "nearest_resize",
     "nearest_resize_bwd", "fold_conv_bn", "bn_stats", "linear_wgrad", "linear_dgrad",
     "dropout_fwd", "dropout_bwd", "dropout_mask", "cross_entropy", "softmax_max", "sgd_",
-    "resize_ragged_u8",
+    "resize_ragged_u8", "png_unfilter",
 ]
 
 
@@ -1131,6 +1131,31 @@ def resize_ragged_u8(data, table, max_hw, c, oh, ow, out="u8", mean=None, std=No
                                   C.cast(sp, C.c_void_p) if sp is not None else None,
                                   _p(y), _p(ws), wsb, stream()), "rr_resize_ragged_u8")
     return y
+
+
+def png_unfilter(data, table, max_hw, out_bytes, out=None):
+    """Undo the PNG row filters of n inflated images and write each as packed
+    RGB (``Image.open(p).convert('RGB')``: 17:69-79, 18:35, 07:52-66, 08:84-88)
+    in one launch.  ``data``: 1-D uint8 device buffer holding the filtered
+    scanlines (kind 1) or raw HWC rows (kind 0) of every image; ``table``:
+    device [n, 32] uint8, n rr_png_image records; ``max_hw`` bounds every
+    image; -> 1-D uint8 device buffer of ``out_bytes`` bytes (``out``, when
+    given, is that buffer: a test hands in a guarded one).  A record that
+    fails rr_png_table_check is skipped: nothing read, nothing written."""
+    _need_cuda(data, table, out)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise TypeError("png_unfilter expects a contiguous 1-D uint8 buffer")
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 32 or not table.is_contiguous():
+        raise TypeError("png_unfilter expects an [n, 32] uint8 table of rr_png_image records")
+    out_bytes = int(out_bytes)
+    if out is None:
+        out = torch.empty(out_bytes, dtype=torch.uint8, device=data.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() != out_bytes:
+        raise TypeError(f"png_unfilter out: expected a contiguous 1-D uint8 buffer of {out_bytes} bytes")
+    L = lib()
+    L.check(L.rr_png_unfilter(int(table.shape[0]), int(max_hw[0]), int(max_hw[1]), _p(data), data.numel(),
+                              _p(table), _p(out), out_bytes, stream()), "rr_png_unfilter")
+    return out
 
 
 def ssim_u8(a, b):

@@ -461,6 +461,96 @@ long long rr_png_encode(int h, int w, int c, const uint8_t *hwc, int level, uint
 int rr_png_write_batch(int n, int h, int w, int c, const uint8_t *hwc, const char *const *paths,
                        int level, int threads);
 
+/* PNG input: the files the reference opens with Image.open(p).convert('RGB')
+ * -- the compound images of 17_run_unified_inference.py:69-79, the restored
+ * images 18_test_unified_benchmark.py:35 points ImageFolder at (written by
+ * rr_png_write_batch), the distorted images of 07_train_restoration.py:52-66
+ * and the mixed *.ppm + *.png list of 08_run_inference.py:84-88.  The host
+ * does the file read and the zlib inflate (rr_png_probe, rr_png_inflate: host
+ * memory only, no device, one file per thread at a time); the device undoes
+ * the row filters and converts to RGB for the whole batch in one launch
+ * (rr_png_unfilter), into the buffer rr_resize_ragged_u8 consumes.
+ *
+ * Accepted files: bit depth 8, colour type 0 (grey), 2 (RGB), 4 (grey +
+ * alpha) or 6 (RGBA), no interlace.  Well-formed palette, 1/2/4/16-bit and
+ * Adam7 files: RR_EUNSUPPORTED; anything malformed: RR_EINVAL.  info[i]
+ * .status holds that code per file and .reason (rr_png_reason) what was
+ * wrong; the calls return RR_OK or the status of the first file that failed
+ * (RR_EINVAL for bad arguments).
+ *
+ * rr_png_probe reads the signature and IHDR of each file: h, w and the file's
+ * channel count (1, 2, 3 or 4).  h, w and h * (1 + w * channels) are checked
+ * in 64-bit before anyone sizes a buffer from them.
+ *
+ * rr_png_inflate concatenates the IDAT chunks of file i (any number, any
+ * length), checks every chunk's CRC, skips ancillary chunks, and inflates
+ * into dst + images_host[i].src.  The record must give the file's own h, w
+ * and channels with kind 1, and its slot h * (1 + w * channels) must lie in
+ * [0, dst_bytes): the stream must inflate to exactly that many bytes, nothing
+ * is written outside the slot, and every row's filter byte must be <= 4 (so
+ * the device never meets another).  Records of kind 0 are left alone. */
+enum rr_png_reason {
+  RR_PNG_OK = 0,
+  RR_PNG_EOPEN = 1,      /* cannot open / read the file                      */
+  RR_PNG_ESIGNATURE = 2, /* not a PNG signature                              */
+  RR_PNG_ETRUNCATED = 3, /* the file ends inside a chunk or before IEND      */
+  RR_PNG_ECRC = 4,       /* a chunk's CRC does not match                     */
+  RR_PNG_EHEADER = 5,    /* malformed IHDR (zero / oversize extent, illegal
+                            depth, colour type, method or interlace value)  */
+  RR_PNG_EKIND = 6,      /* legal but unsupported: palette, 1/2/4/16 bit,
+                            Adam7                                            */
+  RR_PNG_ECHUNK = 7,     /* chunk framing / order (no IDAT, split IDAT run,
+                            unknown critical chunk, oversize length)         */
+  RR_PNG_EZLIB = 8,      /* the IDAT stream is not a complete zlib stream    */
+  RR_PNG_ESIZE = 9,      /* it inflates to fewer or more bytes than
+                            h * (1 + w * channels)                           */
+  RR_PNG_EFILTER = 10,   /* a row's filter byte is above 4                   */
+  RR_PNG_ESLOT = 11      /* the record does not match the file, or its slot
+                            leaves the buffer                                */
+};
+typedef struct rr_png_info {
+  int32_t h, w, channels; /* from IHDR (0 when it could not be read)         */
+  int32_t status;         /* RR_OK / RR_EINVAL / RR_EUNSUPPORTED             */
+  int32_t reason;         /* rr_png_reason                                   */
+} rr_png_info;            /* 20 bytes */
+
+/* One image of an unfilter batch.  kind 1: h filtered scanlines at in + src,
+ * one filter byte in front of each row of w * channels bytes (what
+ * rr_png_inflate leaves); kind 0: raw HWC rows, h * w * channels bytes (a
+ * PPM payload).  Its h * w * 3 RGB bytes go to out + dst. */
+typedef struct rr_png_image {
+  int64_t src;            /* byte offset of the image's first byte in `in`   */
+  int64_t dst;            /* byte offset of its first output pixel in `out`  */
+  int32_t h, w;
+  int32_t channels;       /* 1 grey, 2 grey + alpha, 3 RGB, 4 RGBA           */
+  int32_t kind;           /* 1 filtered scanlines, 0 raw rows                */
+} rr_png_image;           /* 32 bytes */
+
+int rr_png_probe(int n, const char *const *paths, rr_png_info *info, int threads);
+int rr_png_inflate(int n, const char *const *paths, const rr_png_image *images_host, uint8_t *dst,
+                   size_t dst_bytes, rr_png_info *info, int threads);
+
+/* Host-side test of an unfilter table (no launch), the mirror of
+ * rr_ragged_check: RR_EINVAL for bad arguments or a record whose size leaves
+ * [1, max_h] x [1, max_w], whose channels / kind are not the above, or whose
+ * source range [src, src + h * (kind + w * channels)) or destination range
+ * [dst, dst + h * w * 3) leaves its buffer; RR_EUNSUPPORTED for max_w above
+ * 8192 (one reconstructed row is kept on chip between bands). */
+int rr_png_table_check(int n, size_t in_bytes, size_t out_bytes, const rr_png_image *images_host,
+                       int max_h, int max_w);
+
+/* Undo the PNG row filters (PNG spec section 9: None, Sub, Up, Average,
+ * Paeth, chosen per row) of n images and write each as packed RGB, as
+ * Image.open(p).convert('RGB') gives it: grey replicated to three channels,
+ * alpha dropped (not multiplied in), RGB copied; kind 0 records are converted
+ * the same way without the unfilter.  One launch whatever n is, no per-image
+ * host work, graph-capturable: images_dev (device memory) is read on the
+ * device only.  A record that fails rr_png_table_check is skipped: nothing of
+ * it is read and nothing written. */
+int rr_png_unfilter(int n, int max_h, int max_w, const uint8_t *in, size_t in_bytes,
+                    const rr_png_image *images_dev, uint8_t *out, size_t out_bytes,
+                    rr_stream stream);
+
 /* F.interpolate(x, size=(ho, wo)) mode 'nearest' on NHWC [n][hi][wi][C]
  * (ResUNet decoder skip alignment, 14:169-182; C % 4 == 0): ATen's source
  * index min(floor(o * (float)hi / ho), hi - 1) (identity / o >> 1 at equal /
