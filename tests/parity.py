@@ -449,3 +449,301 @@ def intact(buf):
         return bool(torch.isnan(lo).all() and torch.isnan(hi).all())
     want = torch.full((), buf.poison, dtype=buf.raw.dtype, device=buf.raw.device)
     return bool((lo == want).all() and (hi == want).all())
+
+
+# ---------------------------------------------------------------------------
+# the BN backward family (csrc/bn.hip: rr_bn_bwd_reduce / _reduce_gm /
+# _finalize / _apply, all mask kinds, one or two BNs, train and eval mode),
+# the residual / PReLU affine forward, the column sums, and the fused
+# final-conv tail (rr_conv_out_bwd_bnred + rr_bn_bwd_apply_convout)
+#
+# The reduce skeleton.  A workgroup sums its own rows in fp32 (per-thread
+# chains, an LDS pass over the thread rows) into ONE partial row; the partial
+# rows are summed in fp64 (the finalize; the tests sum the slab in fp64
+# themselves).  So no fp32 sum has more than ``n_sum`` = rows_per_block =
+# ceil(P / blocks) terms per channel, and the any-order bound (n - 1) u
+# sum|term| holds block by block: in all, n_sum u sum_p |term_p|.  ``n_sum``
+# defaults to P (one fp32 sum of everything, the model of stats_bound).  The
+# fp64 sum of <= 1024 rows adds 1024 2^-53, inside the u the count leaves over
+# ((n - 1) needed, n charged).
+#
+# gm and its error e_p as the sums see it.  g carries e_g (0 for a plain
+# tensor; u |g + unpool| for the one fp32 add of kinds 3 and 5; the stored
+# bound of the recomputed final-conv grad).  A keep-mask is a tensor of its
+# own once its sign is unambiguous (``sign_ambiguous`` for kind 2,
+# ``sign_ambiguous2`` for the recomputed mask of kinds 4 and 5; an ``aux > 0``
+# mask of a stored tensor is exact): kept elements keep e_g, dropped ones are
+# exactly 0, and the PReLU slope of kind 2 is one fp32 product,
+# |alpha| e_g + u |alpha g|.  rr_bn_bwd_reduce_gm sums the STORED gm: e_p is
+# then the stored bound.
+#
+# Column sums [c, 3] = (sum gm, sum gm xhat0, sum gm xhat1), xhat_i = (t_i -
+# mean_i) invstd_i in fp32: two roundings, both relative to the result (the
+# subtraction is rounded once, the product once), and the product gm xhat one
+# more: 3 u |gm xhat| per term.
+#   sum gm:        sum_p e_p            + n_sum u sum_p |gm_p|
+#   sum gm xhat_i: sum_p e_p |xhat_i,p| + (n_sum + 4) u sum_p |gm_p xhat_i,p|
+# (3 for the term, 1 for the second order).
+#
+# The alpha sum of kind 2, sum over u_p <= 0 of g_p u_p over pixels AND
+# channels: bn.hip sums it in fp32 per workgroup (n_sum C terms) and in fp64
+# across.  The fp32 u_p is within d_p = 2 u (|t_p s| + |b|) of the exact one,
+# the product is rounded once:
+#   sum_{u <= 0} (e_g |u_p| + |g_p| d_p + 2 u |g_p u_p|) + n_sum C u sum |g_p u_p|
+#
+# The finalize is fp64 and stores fp32 (``cast32``): dbeta_i = sum gm,
+# dgamma_i = sum gm xhat_i, dalpha; coef [c][2][3] = (a_i = gamma_i invstd_i
+# as an fp32 product, m0 = sum gm / P, m_i = sum gm xhat_i / P); eval mode
+# divides by +inf: m0 = m_i = 0 exactly, and dbias_i = a_i * (float) sum gm
+# (three fp32 roundings: 4 u with the second order).
+#
+# The apply.  Train: dt_i = a_i (gm - m0 - xhat_i m_i); eval: dt_i = a_i gm.
+# The 8-channel kernel folds it to A gm + B t + D with q = a m inv, B = -q, D
+# = fma(q, mean, -a m0) and two fmas; the 4-channel kernel evaluates it as
+# written.  Either way at most 7 fp32 roundings touch any one of the four terms
+# a gm, a m0, q t, q mean, each relative to a value no larger than their
+# magnitudes' sum: 8 u (|a| (|gm| + |m0| + |m_i| inv (|t| + |mean|))), as
+# pool_bwd_bounds.  Added to a e_p (the apply's own gm: unrounded except where
+# it reads the stored one) and a (sums' bounds / P) through m0 and m_i; one
+# store.
+
+def _col(x):
+    return x.reshape(-1, x.shape[-1]).sum(0)
+
+
+_Z = torch.zeros((), dtype=torch.float64)
+
+
+def sign_ambiguous2(t0, s0, b0, t1, s1, b1):
+    """elements whose fp32 v = (t0 s0 + b0) + (t1 s1 + b1) (the recomputed
+    ReLU mask of kinds 4 and 5, the residual tail's forward) can differ in
+    sign from the exact one under any contraction choice: each affine is within
+    2 u (|t s| + |b|) of exact, the add rounds once more (relative to v: it
+    cannot change a sign): |v| <= 4 u (|t0 s0| + |b0| + |t1 s1| + |b1|), or
+    v = 0.  t s is exact in fp64 (8 or 24 bits times 24); the three fp64 adds
+    are 2^-29 of the threshold."""
+    p0, p1 = t0.double() * s0.double(), t1.double() * s1.double()
+    b0, b1 = b0.double(), b1.double()
+    v = (p0 + b0) + (p1 + b1)
+    return (v.abs() <= 4.0 * U * (p0.abs() + b0.abs() + p1.abs() + b1.abs())) | (v == 0)
+
+
+def _away(t, dtype):
+    ity = torch.int16 if dtype == torch.bfloat16 else torch.int32
+    return (t.to(dtype).view(ity) + 1).view(dtype).float()          # sign-magnitude: one ulp away from zero
+
+
+def make_sign_unambiguous2(t0, s0, b0, t1, s1, b1, dtype=torch.bfloat16):
+    """(t0', moved): t0 with every ambiguous element moved to the neighbouring
+    value of ``dtype`` away from zero, repeated until none is left; ``moved``
+    marks the elements that changed"""
+    t = t0.float().clone()
+    for _ in range(8):
+        bad = sign_ambiguous2(t, s0, b0, t1, s1, b1)
+        if not bool(bad.any()):
+            break
+        t = torch.where(bad, _away(t, dtype), t)
+    return t, t != t0.float()
+
+
+def unpooled(pdy, idx, h, w):
+    """the MaxPool2d(2) backward of pdy [n, h/2, w/2, c] through the window
+    index idx = 2 dy + dx, fp64 [n, h, w, c]"""
+    pdy = pdy.double()
+    n, _, _, c = pdy.shape
+    up = torch.zeros(n, h, w, c, dtype=torch.float64)
+    win = up.view(n, h // 2, 2, w // 2, 2, c)
+    for k in range(4):
+        win[:, :, k // 2, :, k % 2, :] = torch.where(idx == k, pdy, _Z)
+    return up
+
+
+def bn_bwd_bounds(g, keep, t, mean, invstd, gamma, out_dtype, eval_mode=False, slope=None, u=None, du=None,
+                  e_g=None, n_sum=None, sum_stored=False):
+    """The general BN backward of nbn = len(t) BatchNorms fed by one gm.
+    g [..., c] the upstream grad (fp64, with the bound ``e_g`` or exact), keep
+    the boolean mask computed by the caller (kinds 0: all true; 1, 3: aux > 0;
+    4, 5: the recomputed v > 0; 2: u > 0), ``slope`` the PReLU slope of kind 2
+    with u = t s + b (fp64) and ``du`` the bound of its fp32 value; t, mean,
+    invstd, gamma lists of nbn tensors.  ``sum_stored``: the sums are taken of
+    the stored gm, which the apply then reads (rr_bn_bwd_reduce_gm).  Returns {name: (ref64, bound64)} of gm, sums [c, 3], coef [c,
+    2, 3], dgamma0/1, dbeta0/1, dt0/1, with a slope alpha (the fp64 sum) and
+    dalpha, in eval mode dbias0/1.  The derivation is above."""
+    nbn = len(t)
+    assert nbn in (1, 2) and len(mean) == len(invstd) == len(gamma) == nbn
+    g = g.double()
+    c = g.shape[-1]
+    P = g.numel() // c
+    n_sum = P if n_sum is None else int(n_sum)
+    e_g = torch.zeros_like(g) if e_g is None else e_g.double()
+    if slope is None:
+        gm = torch.where(keep, g, _Z)
+        e_raw = torch.where(keep, e_g, _Z)
+    else:
+        assert abs(slope) <= 1 and u is not None and du is not None
+        gm = torch.where(keep, g, slope * g)
+        e_raw = torch.where(keep, e_g, abs(slope) * e_g + U * gm.abs())
+    gm_b = _stored(gm, e_raw, out_dtype)
+    e = gm_b if sum_stored else e_raw
+    t = [x.double() for x in t]
+    mean, invstd = [x.double() for x in mean], [x.double() for x in invstd]
+    a = [(torch.ones(c, dtype=torch.float64) if gm_ is None else gm_.double()) * iv for gm_, iv in zip(gamma, invstd)]
+    xhat = [(t[i] - mean[i]) * invstd[i] for i in range(nbn)]
+    zc = torch.zeros(c, dtype=torch.float64)
+    cols, cols_b = [_col(gm)], [_col(e) + n_sum * U * _col(gm.abs())]
+    for i in range(2):
+        if i < nbn:
+            tx = gm * xhat[i]
+            cols.append(_col(tx))
+            cols_b.append(_col(e * xhat[i].abs()) + (n_sum + 4) * U * _col(tx.abs()))
+        else:
+            cols.append(zc)
+            cols_b.append(zc)                       # one BN: the third column is exactly zero
+    sums, sums_b = torch.stack(cols, 1), torch.stack(cols_b, 1)
+    out = {"gm": (gm, gm_b), "sums": (sums, sums_b)}
+    if slope is not None:
+        neg = ~keep
+        gu = torch.where(neg, g * u, _Z)
+        a_b = torch.where(neg, e_g * u.abs() + g.abs() * du + 2.0 * U * gu.abs(), _Z).sum() \
+            + n_sum * c * U * gu.abs().sum()
+        out["alpha"] = (gu.sum(), a_b)
+        out["dalpha"] = cast32(out["alpha"])
+    coef = torch.zeros(c, 2, 3, dtype=torch.float64)
+    coef_b = torch.zeros_like(coef)
+    for i in range(nbn):
+        s0, s0b, si, sib = sums[:, 0], sums_b[:, 0], sums[:, 1 + i], sums_b[:, 1 + i]
+        out["dbeta%d" % i] = cast32((s0, s0b))
+        out["dgamma%d" % i] = cast32((si, sib))
+        if eval_mode:
+            m0, mi, m0b, mib = zc, zc, zc, zc
+            ref = a[i] * s0
+            out["dbias%d" % i] = (ref, a[i].abs() * s0b + 4.0 * U * (ref.abs() + a[i].abs() * s0b))
+        else:
+            (m0, m0b), (mi, mib) = cast32((s0 / P, s0b / P)), cast32((si / P, sib / P))
+        coef[:, i, 0], coef_b[:, i, 0] = a[i], U * a[i].abs()
+        coef[:, i, 1], coef_b[:, i, 1] = m0, m0b
+        coef[:, i, 2], coef_b[:, i, 2] = mi, mib
+        dt = a[i] * (gm - m0 - xhat[i] * mi)
+        mag = a[i].abs() * (gm.abs() + e + (m0.abs() + m0b) + (mi.abs() + mib) * invstd[i] * (t[i].abs() + mean[i].abs()))
+        ev = a[i].abs() * (e + m0b + xhat[i].abs() * mib) + 8.0 * U * mag
+        out["dt%d" % i] = (dt, _stored(dt, ev, out_dtype))
+    out["coef"] = (coef, coef_b)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# rr_affine_act / rr_affine_act_pool
+#
+#   u = x s + b            fp32, fma or not: within 2 u (|x s| + |b|)
+#   a = PReLU(u)           (when a slope is given) one more fp32 product, u |a|;
+#                          PReLU with |alpha| <= 1 is 1-Lipschitz and continuous,
+#                          so the error of u passes through whatever its sign
+#   r = res rs + rb        within 2 u (|res rs| + |rb|); a plain res is exact
+#   v = a + r              one fp32 add: u |v| (+ second order: u times the errors)
+#   y = ReLU(v)            1-Lipschitz
+# then one store.  Without res the add and r drop out.
+
+def affine_res_bound(x, s, b, out_dtype, alpha=None, res=None, rs=None, rb=None, relu=False):
+    """(ref64, bound64) of y = act(x s + b [+ res | + res rs + rb]) of x
+    [..., c], act in {none, PReLU before the residual (``alpha``), ReLU after
+    (``relu``)}, stored once in ``out_dtype``"""
+    x, s, b = x.double(), s.double(), b.double()
+    v = x * s + b
+    ev = 2.0 * U * ((x * s).abs() + b.abs())
+    if alpha is not None:
+        assert abs(alpha) <= 1
+        v = torch.where(v > 0, v, alpha * v)
+        ev = ev + U * v.abs()
+    if res is not None:
+        r = res.double()
+        if rs is not None:
+            er = 2.0 * U * ((r * rs.double()).abs() + rb.double().abs())
+            r = r * rs.double() + rb.double()
+            ev = ev + er
+        else:
+            assert rb is None
+        v = v + r
+        ev = ev + U * (v.abs() + ev)
+    if relu:
+        v = v.clamp_min(0)
+    return v, _stored(v, ev, out_dtype)
+
+
+def affine_pool_bounds(rb, operands):
+    """The pooled companion of ``affine_res_bound``'s (ref, bound) NHWC ``rb``:
+    (pooled ref, pooled bound) by ``pooled`` (the window max of the STORED
+    values: each within its bound of ref, and the max is 1-Lipschitz), the
+    first-max window index 2 dy + dx of ref, and ``sure`` -- the windows whose
+    index is decided: every other element of the window either lies below the
+    maximum by more than the two bounds (ref_k + bound_k < ref_a - bound_a:
+    then the stored values are ordered the same way), or has bit-identical
+    ``operands`` (x, res, ...: same channel, same arithmetic, the same stored
+    value, and the first of them wins in ref as in the kernel).  Windows with a
+    tie inside the bound are not sure and left out of the index check."""
+    ref, bound = rb
+    n, h, w, c = ref.shape
+
+    def win(t):
+        return t.reshape(n, h // 2, 2, w // 2, 2, c).permute(0, 1, 3, 5, 2, 4).reshape(n, h // 2, w // 2, c, 4)
+    wr, wb = win(ref), win(bound)
+    best = wr.max(-1, keepdim=True).values
+    idx = (wr == best).to(torch.uint8).argmax(-1)                      # the first maximum
+    ra, ba = wr.gather(-1, idx[..., None]), wb.gather(-1, idx[..., None])
+    same = torch.ones_like(wr, dtype=torch.bool)
+    for o in operands:
+        wo = win(o.double())
+        same &= wo == wo.gather(-1, idx[..., None])
+    ok = (wr + wb < ra - ba) | same
+    return pooled(rb), idx.to(torch.uint8), ok.all(-1)
+
+
+# ---------------------------------------------------------------------------
+# rr_channel_sum / rr_bn_stats: plain tensors, e_p = 0 in stats_bound's model,
+# the reduce skeleton above (n_sum terms per fp32 sum, fp64 across).
+
+def colsum_bound(x, n_sum=None, out0=None):
+    """(ref64, bound64) [c] of the column sums of x [P, c], stored fp32 once
+    (``cast32``); with ``out0`` the accumulate form out0 + (float) s: one more
+    fp32 add"""
+    x = x.double()
+    n_sum = x.shape[0] if n_sum is None else int(n_sum)
+    ref, bound = cast32((x.sum(0), n_sum * U * x.abs().sum(0)))
+    if out0 is not None:
+        ref = ref + out0.double()
+        bound = bound + U * (ref.abs() + bound)
+    return ref, bound
+
+
+def colstats_bound(x, n_sum=None):
+    """(ref64, bound64) [c, 2] = (sum, sum of squares) of x [P, c] summed over
+    the partial rows: the squares are fp32 products or the exact product of an
+    fma, one rounding more per term at the most"""
+    x = x.double()
+    n_sum = x.shape[0] if n_sum is None else int(n_sum)
+    q = (x * x).sum(0)
+    return torch.stack((x.sum(0), q), 1), torch.stack((n_sum * U * x.abs().sum(0), (n_sum + 1) * U * q), 1)
+
+
+# ---------------------------------------------------------------------------
+# rr_conv_out_bwd_bnred -> rr_bn_bwd_finalize -> rr_bn_bwd_apply_convout
+
+def convout_tail_bounds(dy, wt, keep, t, mean, invstd, gamma, out_dtype, x, n_sum=None):
+    """The final 1x1 conv's backward fused with the BN backward of the block
+    before it.  dy [n, 3, h, w] fp32 (NCHW), wt [3, c]: g = round_T(sum_co dy
+    w), K = 3 fp32 products of fp32 operands (2 K u A), continuous through the
+    store (``_stored``): the reduce sums that stored g and the apply reads it
+    (both recompute and round it); then ``bn_bwd_bounds`` with nbn = 2 and
+    that bound as e_g.  dw [3, c] = sum_p dy x and db [3] = sum_p dy are K = P
+    sums of fp32 products (``wgrad_bound``'s model), x [n, h, w, c] the block
+    output."""
+    dyn = dy.double().permute(0, 2, 3, 1)                               # [n, h, w, 3]
+    w64 = wt.double()
+    g = dyn @ w64
+    e_acc = 2.0 * 3 * U * (dyn.abs() @ w64.abs())
+    e_g = _stored(g, e_acc, out_dtype)
+    out = bn_bwd_bounds(g, keep, t, mean, invstd, gamma, out_dtype, e_g=e_g, n_sum=n_sum)
+    P = g.numel() // g.shape[-1]
+    d2, x2 = dyn.reshape(P, 3), x.double().reshape(P, -1)
+    out["dw"] = _finish(d2.t() @ x2, d2.abs().t() @ x2.abs(), P, torch.float32, 1)
+    out["db"] = _finish(d2.sum(0), d2.abs().sum(0), P, torch.float32, 1)
+    return out

@@ -252,7 +252,9 @@ def test_wgrad3_halo(dev, hw, halo, monkeypatch):
 def test_igemm_bnbwd_fused(dev, dt, n, h, w, C):
     """conv dgrad + BN/PReLU backward reduce fused in the epilogue
     (rr_igemm_bnbwd + rr_bn_bwd_finalize_rows) == the unfused sequence
-    (rr_igemm, then rr_bn_bwd_reduce/finalize/apply with mask_kind 2)."""
+    (rr_igemm, then rr_bn_bwd_reduce/finalize/apply with mask_kind 2).
+    The unfused side is held per element to fp64 in
+    tests/test_bn_elementwise_gpu.py (mask kind 2, both kernel widths)."""
     import roadrestore as rr
     from roadrestore._lib import RR_CONV3X3
     ops = rr.ops
@@ -392,7 +394,9 @@ def test_convT(dev, dt):
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_bn_train_fwd_bwd(dev, dt):
     """BatchNorm2d train fwd (batch stats, running update) + PReLU, and the
-    fused backward (mask kinds 1 and 2)."""
+    fused backward (mask kinds 1 and 2).  Norms against torch autograd; the
+    per-element fp64 bounds of the BN backward, every mask kind and shape
+    edge, are in tests/test_bn_elementwise_gpu.py."""
     import roadrestore as rr
     from roadrestore._lib import RR_CONV3X3
     n, h, w, cin, C = 4, 8, 8, 64, 64
