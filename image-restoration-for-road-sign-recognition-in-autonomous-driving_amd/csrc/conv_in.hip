@@ -133,9 +133,22 @@ __global__ void conv_in_wgrad_kernel(int n, int h, int w, int cin, int cout,
 // staged per step in LDS from the image (zero padded).  Per block:
 // a fixed pixel range -> one [64][32] partial slab (+ a dalpha row), reduced
 // by rr_colreduce + conv_in_wgrad_act_finalize in fixed order.
+//
+// REC: the pre-activation t is not read but recomputed per step from the
+// staged patch and the packed first-layer weights (`t` then points at the
+// kpad-32 pack the forward used, [64][32] bf16): conv_in_mfma_kernel's own
+// MFMA -- A = the pack's rows (wave wv: channels 16 wv .. +15), B = 16 pixels
+// x 32 patch entries with the ones column at k = 27, zero accumulator --
+// rounded to bf16 as the forward stored it, so gp, the dalpha sum and gT are
+// formed from the same bits in the same order.  The patch is staged a second
+// time pixel-major (pX) for that B fragment; t goes through gT's own words
+// (channel rows, the (lc, lpp) thread reads exactly the words it then
+// overwrites with gp).
 constexpr int CIA_NPX = 64;
 constexpr int CIA_ROW = CIA_NPX + 8;                  // bf16 per LDS row (144 B)
-__global__ __launch_bounds__(256) void conv_in_wgrad_act_kernel(
+constexpr int CIA_XROW = 32 + 8;                      // bf16 per pixel-major patch row (80 B)
+template <bool REC>
+__global__ __launch_bounds__(256, REC ? 4 : 1) void conv_in_wgrad_act_kernel(
     int n, int h, int w, const float *__restrict__ x, const bf16_t *__restrict__ g,
     const bf16_t *__restrict__ t, int act, const float *__restrict__ alpha,
     float *__restrict__ part, long long ppb) {
@@ -143,6 +156,7 @@ __global__ __launch_bounds__(256) void conv_in_wgrad_act_kernel(
   // (27 image taps, a ones row, 4 zero rows) of the same pixels, bf16
   __shared__ __attribute__((aligned(16))) u16 gT[64 * CIA_ROW];
   __shared__ __attribute__((aligned(16))) u16 pT[32 * CIA_ROW];
+  __shared__ __attribute__((aligned(16))) u16 pX[REC ? CIA_NPX * CIA_XROW : 8];
   __shared__ float red[256];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long P = (long long)n * h * w, hw = (long long)h * w;
@@ -154,7 +168,7 @@ __global__ __launch_bounds__(256) void conv_in_wgrad_act_kernel(
   const int bn = lane & 15, bk = lane >> 4;           // fragment col / k-block
   const int sj = tid & 63, sg = tid >> 6;             // patch staging: pixel, row group
   // registers of one step's operands, loaded a step ahead of their use
-  uint4 rg[2], rt[2];
+  uint4 rg[2], rt[2] = {};
   float rp[8];
   auto load_step = [&](long long q0) __attribute__((always_inline)) {
 #pragma unroll
@@ -163,7 +177,7 @@ __global__ __launch_bounds__(256) void conv_in_wgrad_act_kernel(
       const bool ok = p < p1;
       const long long e = (ok ? p : p0) * 64 + lc * 8;
       rg[j] = *reinterpret_cast<const uint4 *>(g + e);
-      rt[j] = *reinterpret_cast<const uint4 *>(t + e);
+      if constexpr (!REC) rt[j] = *reinterpret_cast<const uint4 *>(t + e);
       if (!ok) rg[j] = uint4{0u, 0u, 0u, 0u};
     }
     const long long p = q0 + sj;
@@ -192,17 +206,46 @@ __global__ __launch_bounds__(256) void conv_in_wgrad_act_kernel(
     }
   };
   auto bf = [](uint32_t word, int hi) { return __uint_as_float(hi ? (word & 0xffff0000u) : (word << 16)); };
+  // REC: the wave's weight fragment, rows co = 16 wv + bn, k = 8 bk .. +7
+  bf16x8 fw = {};
+  if constexpr (REC) fw = *reinterpret_cast<const bf16x8 *>(t + (wv * 16 + bn) * 32 + bk * 8);
   if (p0 < p1) load_step(p0);
   for (long long q0 = p0; q0 < p1; q0 += CIA_NPX) {
+    if constexpr (REC) {
+      // ---- the patch, both layouts; t = W patch for the wave's 16 channels
+      // ---- x 64 pixels -> gT[co][px]; read back in the (lc, lpp) mapping
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const u16 pv = f32_to_bf16(rp[u]);
+        pT[(sg + 4 * u) * CIA_ROW + sj] = pv;
+        pX[sj * CIA_XROW + sg + 4 * u] = pv;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        const bf16x8 fp = *reinterpret_cast<const bf16x8 *>(&pX[(nb * 16 + bn) * CIA_XROW + bk * 8]);
+        const f32x4 tv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw, fp, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) gT[(wv * 16 + 4 * bk + i) * CIA_ROW + nb * 16 + bn] = f32_to_bf16(tv[i]);
+      }
+      __syncthreads();
+    }
     // ---- gp for pixels q0 + 2 lpp, +1, channels 8 lc .. +7 -> gT[co][px] ----
     u16 v[2][8];
+    uint32_t tpair[8];                                  // REC: t of (px 2 lpp, +1) per channel
+    if constexpr (REC) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        tpair[k] = *reinterpret_cast<const uint32_t *>(&gT[(lc * 8 + k) * CIA_ROW + 2 * lpp]);
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const uint32_t gw[4] = {rg[j].x, rg[j].y, rg[j].z, rg[j].w};
       const uint32_t tw[4] = {rt[j].x, rt[j].y, rt[j].z, rt[j].w};
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float gg = bf(gw[k >> 1], k & 1), tt = bf(tw[k >> 1], k & 1);
+        const float gg = bf(gw[k >> 1], k & 1);
+        const float tt = REC ? bf(tpair[k], j) : bf(tw[k >> 1], k & 1);
         const float gp = tt > 0.f ? gg : al * gg;
         sa += tt > 0.f ? 0.f : gg * tt;
         v[j][k] = f32_to_bf16(gp);
@@ -212,8 +255,10 @@ __global__ __launch_bounds__(256) void conv_in_wgrad_act_kernel(
     for (int k = 0; k < 8; ++k)
       *reinterpret_cast<uint32_t *>(&gT[(lc * 8 + k) * CIA_ROW + 2 * lpp]) =
           (uint32_t)v[0][k] | ((uint32_t)v[1][k] << 16);
+    if constexpr (!REC) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) pT[(sg + 4 * u) * CIA_ROW + sj] = f32_to_bf16(rp[u]);
+      for (int u = 0; u < 8; ++u) pT[(sg + 4 * u) * CIA_ROW + sj] = f32_to_bf16(rp[u]);
+    }
     __syncthreads();
     if (q0 + CIA_NPX < p1) load_step(q0 + CIA_NPX);     // next step's operands in flight
     // ---- MFMA: wave wv owns channels 16 wv .. +15, both 32-pixel k-steps ----
@@ -555,10 +600,10 @@ extern "C" size_t rr_conv_in_wgrad_act_workspace(int n, int h, int w) {
   return (size_t)blocks * (64 * 32 + 32) * sizeof(float) + rr_colreduce_bytes(blocks, 64 * 32 + 32);
 }
 
-extern "C" int rr_conv_in_wgrad_act(int n, int h, int w, const float *x, const void *dy,
-                                    const void *t_pre, int act, const float *alpha, float *dw,
-                                    float *db, float *dalpha, void *ws, size_t ws_bytes,
-                                    rr_stream stream) {
+// rec: t_pre is the forward's kpad-32 weight pack, the pre-activation recomputed
+static int conv_in_wgrad_act(bool rec, int n, int h, int w, const float *x, const void *dy,
+                             const void *t_pre, int act, const float *alpha, float *dw, float *db,
+                             float *dalpha, void *ws, size_t ws_bytes, rr_stream stream) {
   if (!x || !dy || !t_pre || !dw || n <= 0 || h <= 0 || w <= 0) return RR_EINVAL;
   if (act < 1 || act > 2 || (act == 2 && !alpha)) return RR_EINVAL;
   const long long P = (long long)n * h * w;
@@ -568,8 +613,12 @@ extern "C" int rr_conv_in_wgrad_act(int n, int h, int w, const float *x, const v
   long long ppb = (P + blocks - 1) / blocks;
   ppb = (ppb + CIA_NPX - 1) / CIA_NPX * CIA_NPX;            // whole 64-pixel steps (8-aligned)
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(conv_in_wgrad_act_kernel, dim3(blocks), dim3(256), 0, st, n, h, w, x,
-                     (const bf16_t *)dy, (const bf16_t *)t_pre, act, alpha, (float *)ws, ppb);
+  if (rec)
+    hipLaunchKernelGGL(conv_in_wgrad_act_kernel<true>, dim3(blocks), dim3(256), 0, st, n, h, w, x,
+                       (const bf16_t *)dy, (const bf16_t *)t_pre, act, alpha, (float *)ws, ppb);
+  else
+    hipLaunchKernelGGL(conv_in_wgrad_act_kernel<false>, dim3(blocks), dim3(256), 0, st, n, h, w, x,
+                       (const bf16_t *)dy, (const bf16_t *)t_pre, act, alpha, (float *)ws, ppb);
   RR_CHECK_LAUNCH();
   double *red = (double *)((char *)ws + pbytes);
   const int chunks = rr_colreduce_misc((const float *)ws, blocks, 64 * 32 + 32, red, st);
@@ -578,6 +627,20 @@ extern "C" int rr_conv_in_wgrad_act(int n, int h, int w, const float *x, const v
                      chunks, (const double *)red, dw, db, act == 2 ? dalpha : nullptr);
   RR_CHECK_LAUNCH();
   return RR_OK;
+}
+
+extern "C" int rr_conv_in_wgrad_act(int n, int h, int w, const float *x, const void *dy,
+                                    const void *t_pre, int act, const float *alpha, float *dw,
+                                    float *db, float *dalpha, void *ws, size_t ws_bytes,
+                                    rr_stream stream) {
+  return conv_in_wgrad_act(false, n, h, w, x, dy, t_pre, act, alpha, dw, db, dalpha, ws, ws_bytes, stream);
+}
+
+extern "C" int rr_conv_in_wgrad_act_rec(int n, int h, int w, const float *x, const void *dy,
+                                        const void *wpack32, int act, const float *alpha, float *dw,
+                                        float *db, float *dalpha, void *ws, size_t ws_bytes,
+                                        rr_stream stream) {
+  return conv_in_wgrad_act(true, n, h, w, x, dy, wpack32, act, alpha, dw, db, dalpha, ws, ws_bytes, stream);
 }
 
 extern "C" int rr_conv_in_dgrad(int dtype, int n, int h, int w, int cin, int cout, const void *dy,

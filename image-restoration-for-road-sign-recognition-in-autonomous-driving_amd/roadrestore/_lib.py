@@ -186,6 +186,7 @@ _SIGS = {
     "rr_conv_in_wgrad_workspace": (S_, [I_, I_, I_, I_, I_]),
     "rr_conv_in_wgrad_act_workspace": (S_, [I_, I_, I_]),
     "rr_conv_in_wgrad_act": (I_, [I_, I_, I_, P_, P_, P_, I_, P_, P_, P_, P_, P_, S_, P_]),
+    "rr_conv_in_wgrad_act_rec": (I_, [I_, I_, I_, P_, P_, P_, I_, P_, P_, P_, P_, P_, S_, P_]),
     "rr_conv_in_dgrad": (I_, [I_, I_, I_, I_, I_, I_, P_, P_, P_, I_, P_]),
     "rr_prelu_bwd": (I_, [I_, L_, P_, P_, P_, P_, P_, I_, P_, P_]),
     "rr_conv_out_fwd": (I_, [I_, I_, I_, I_, I_, I_, P_, P_, P_, P_, P_]),
@@ -196,7 +197,10 @@ _SIGS = {
                                    P_, P_, P_, P_, P_, S_, P_]),
     "rr_bn_bwd_apply_convout": (I_, [C.POINTER(BnBwdDesc), I_, I_, P_, P_, I_, P_, P_, P_, P_, P_, P_, P_,
                                      P_, P_, P_, P_, P_]),
-    "rr_nchw_to_nhwc": (I_, [I_, I_, I_, I_, I_, P_, P_, P_]),
+    "rr_conv_out_bwd_bnred_rec": (I_, [I_, I_, I_, I_, C.POINTER(BnBwdDesc), P_, P_, P_, P_, P_, P_, P_,
+                                       P_, P_, P_, P_, P_, P_, P_, S_, P_]),
+    "rr_affine_act_conv_out": (I_, [I_, I_, I_, I_, I_, I_, P_, P_, P_, P_, P_, P_, P_, P_, P_, P_, P_]),
+    "rr_nchw_to_nhwc": (I_,[I_, I_, I_, I_, I_, P_, P_, P_]),
     "rr_nhwc_to_nchw": (I_, [I_, I_, I_, I_, I_, P_, P_, P_]),
     "rr_loss_fwd": (I_, [I_, I_, L_, P_, P_, P_, F_, I_, P_, S_, P_]),
     "rr_loss_workspace": (S_, [L_]),

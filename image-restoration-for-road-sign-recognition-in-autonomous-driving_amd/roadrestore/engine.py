@@ -531,9 +531,16 @@ def _ex_fusable(dtype, n, h, w, c1, c2, cout, act, accumulate=False):
     return (fused.startswith("conv3r") or fused.startswith("stream3")) and fused == plain
 
 
-def resblock_forward(blk, x1, x2, n, h, w, wc, dt, training, need_bwd, pool=False):
+def resblock_forward(blk, x1, x2, n, h, w, wc, dt, training, need_bwd, pool=False, tail_conv=None):
     """-> (out, S), or (out, S, (pooled, idx)) with ``pool`` (the 2x2 max-pool
-    that follows the encoder blocks, fused into the residual tail)."""
+    that follows the encoder blocks, fused into the residual tail).
+
+    ``tail_conv=final``: the block's output feeds only the 1x1 conv
+    ``final``.  Where the recompute path is taken (decided here, once, and
+    recorded as ``S.tail_rec``) the tail and that conv run as one pass, the
+    block output is never stored -- ``out`` and ``S.out`` are None, the conv's
+    result is ``S.tail_out`` -- and the backward recomputes it
+    (``resblock_backward(convout=...)`` follows ``S.tail_rec``)."""
     if _FOLD_BN and not training and not need_bwd:
         return resblock_forward_eval_folded(blk, x1, x2, n, h, w, wc, dt, pool)
     cb = blk.conv_block
@@ -587,7 +594,19 @@ def resblock_forward(blk, x1, x2, n, h, w, wc, dt, training, need_bwd, pool=Fals
         s2, sh2, m2, i2 = _bn_affine(bn2, st2, c2.bias, P, training, out=out2, need_bwd=need_bwd)
         res, rsc, rsh = x1, None, None
     pooled = None
-    if pool and _FUSED_POOL and h % 2 == 0 and w % 2 == 0 and cout % 8 == 0:
+    S.tail_rec = False
+    if tail_conv is not None and _RECOMPUTE_TAIL and _FUSED_CONVOUT_BN and pair is not None and \
+            training and need_bwd and not pool and \
+            ops.affine_act_conv_out_ok(t2, tail_conv.weight.shape[0]):
+        final = tail_conv
+        fused = ops.affine_act_conv_out(t2, s2, sh2, res, rsc, rsh,
+                                        wc.conv(final.weight, dt, dgrad=False)[0], final.bias,
+                                        final.weight.shape[0], want_y=False)
+        if fused is not None:
+            S.tail_rec, S.tail_out = True, fused[1]
+    if S.tail_rec:
+        out = None
+    elif pool and _FUSED_POOL and h % 2 == 0 and w % 2 == 0 and cout % 8 == 0:
         out, yp, idx = ops.affine_act_pool(t2, s2, sh2, res=res, res_scale=rsc, res_shift=rsh, relu=True)
         pooled = (yp, idx)
     else:
@@ -646,10 +665,15 @@ def resblock_backward(blk, S, g_out, sink, pool=None, convout=None, reduce_side=
         r = None
         if convout is not None:
             final, dy = convout
-            if _FUSED_CONVOUT_BN and rec is not None and not ev and pool is None:
+            if S.get("tail_rec") and (rec is None or ev or pool is not None):
+                raise RuntimeError("the forward left the block output to be recomputed")
+            if (_FUSED_CONVOUT_BN or S.get("tail_rec")) and rec is not None and not ev and pool is None:
+                # (S.out None: the forward chose the recompute, S.tail_rec)
                 r = ops.bn_backward_convout(dy, S.out, final.weight, S.t2, S.m2, S.i2, bn2.weight,
                                             S.s, S.ms, S.is_, sc1.weight, rec, outs2,
                                             dw=sink[final.weight], db=sink[final.bias])
+            if r is None and S.get("tail_rec"):
+                raise RuntimeError("the forward left the block output to be recomputed")
             if r is None:
                 g_out, _, _ = ops.conv_out_bwd(dy, S.out, final.weight, mask_relu=False,
                                                dw=sink[final.weight], db=sink[final.bias])
@@ -751,12 +775,19 @@ def resunet_forward(m, x, wc, dt, training, need_bwd):
     H4, W4 = H3 // 2, W3 // 2
     S = Bag(n=n, H=H, W=W, x=x, sizes=((H, W), (H2, W2), (H3, W3), (H4, W4)))
     pr = m.enc1[1]
-    # conv + PReLU in one pass (the pre-activation kept for the PReLU backward)
-    e1, e1pre = ops.first_conv_fwd(x, m.enc1[0].weight, m.enc1[0].bias, dt,
-                                   wc.conv_in(m.enc1[0].weight, m.enc1[0].bias, dt), act=2,
-                                   alpha=pr.weight, want_pre=need_bwd)
+    # conv + PReLU in one pass; the pre-activation is kept for the PReLU
+    # backward, or -- decided here, once, and recorded as S.e1_rec -- left
+    # unstored where the fused first-conv backward will recompute it from the
+    # image patch and this very pack (rr_conv_in_wgrad_act_rec)
+    e1pack = wc.conv_in(m.enc1[0].weight, m.enc1[0].bias, dt)
+    S.e1_rec = bool(need_bwd and _RECOMPUTE_FIRST and _FUSED_FIRST_WGRAD and dt == torch.bfloat16 and
+                    W % 8 == 0 and ops.conv_in_kpad(dt, x.shape[1], m.enc1[0].weight.shape[0]) ==
+                    ops.KPAD_MFMA and hasattr(ops.lib(), "rr_conv_in_wgrad_act_rec"))
+    e1, e1pre = ops.first_conv_fwd(x, m.enc1[0].weight, m.enc1[0].bias, dt, e1pack, act=2,
+                                   alpha=pr.weight, want_pre=need_bwd and not S.e1_rec)
     if need_bwd:
         S.e1pre = e1pre
+        S.e1pack = e1pack if S.e1_rec else None
     r1, S.res1, (p1, i1) = resblock_forward(m.res1, e1, None, n, H, W, wc, dt, training, need_bwd,
                                             pool=True)
     r2, S.res2, (p2, i2) = resblock_forward(m.res2, p1, None, n, H2, W2, wc, dt, training,
@@ -775,9 +806,15 @@ def resunet_forward(m, x, wc, dt, training, need_bwd):
     d2, S.dec2 = resblock_forward(m.dec2, u2, r2, n, H2, W2, wc, dt, training, need_bwd)
     u1, pku1 = _convT_up(wc, dt, m.up1, d2, n, H2, W2, need_bwd)
     u1, al1 = _skip_align(u1, H, W)
-    d1, S.dec1 = resblock_forward(m.dec1, u1, r1, n, H, W, wc, dt, training, need_bwd)
-    out = ops.conv_out_fwd(d1, m.final.weight, m.final.bias,
-                           wpack=wc.conv(m.final.weight, dt, dgrad=False)[0])
+    # dec1's output feeds the final conv alone: one pass for its residual tail
+    # and that conv where the block output can be recomputed in the backward
+    d1, S.dec1 = resblock_forward(m.dec1, u1, r1, n, H, W, wc, dt, training, need_bwd,
+                                  tail_conv=m.final)
+    if S.dec1.get("tail_rec"):
+        out = S.dec1.tail_out
+    else:
+        out = ops.conv_out_fwd(d1, m.final.weight, m.final.bias,
+                               wpack=wc.conv(m.final.weight, dt, dgrad=False)[0])
     if need_bwd:
         S.update(e1=e1, r1=r1, r2=r2, r3=r3, i1=i1, i2=i2, i3=i3, b=b, d3=d3, d2=d2, d1=d1,
                  pku3=pku3, pku2=pku2, pku1=pku1, aligned=(al1, al2, al3))
@@ -820,6 +857,13 @@ _SPLIT_DGRAD = path_flag("split_dgrad", 1) != 0
 # A/B switch: the final conv's backward fused with dec1's tail BN reduce, its
 # input grad recomputed in the apply instead of stored (rr_conv_out_bwd_bnred)
 _FUSED_CONVOUT_BN = path_flag("convout_bn", 1) != 0
+# A/B switch: dec1's residual tail + the final conv as one pass that does not
+# store the block output; the final conv's backward recomputes it
+# (rr_affine_act_conv_out / rr_conv_out_bwd_bnred_rec; 0: today's three passes)
+_RECOMPUTE_TAIL = path_flag("recompute_tail", 1) != 0
+# A/B switch: the first conv's pre-activation not stored; the fused first-conv
+# backward recomputes it (rr_conv_in_wgrad_act_rec; 0: stored and read back)
+_RECOMPUTE_FIRST = path_flag("recompute_first", 1) != 0
 # A/B switch: ... each with the shortcut's 1x1 dgrad summed in (rr_igemm_dgrad_sc)
 _FUSED_SC_DGRAD = path_flag("sc_dgrad", 1) != 0
 
@@ -912,7 +956,11 @@ def resunet_backward(m, S, g_out, sink):
         ops.maxpool2_bwd(g_p1, S.i1, H, W, out=g_r1, accumulate=True)
         g_e1, _ = resblock_backward(m.res1, S.res1, g_r1, sink, reduce_side=sd)
     pr = m.enc1[1]
-    if g_e1.dtype == torch.bfloat16 and W % 8 == 0 and _FUSED_FIRST_WGRAD:
+    if S.get("e1_rec"):
+        # (the forward's choice: no stored pre-activation, the forward's pack)
+        ops.first_conv_wgrad_act(S.x, g_e1, None, 2, pr.weight, sink[m.enc1[0].weight],
+                                 sink[m.enc1[0].bias], dalpha=sink[pr.weight], wpack=S.e1pack)
+    elif g_e1.dtype == torch.bfloat16 and W % 8 == 0 and _FUSED_FIRST_WGRAD:
         # PReLU backward + first-conv wgrad in one pass over the image
         ops.first_conv_wgrad_act(S.x, g_e1, S.e1pre, 2, pr.weight, sink[m.enc1[0].weight],
                                  sink[m.enc1[0].bias], dalpha=sink[pr.weight])

@@ -13,7 +13,7 @@ import ctypes as C
 import torch
 
 from ._lib import (path_flag, RR_ACT_NOFULL, RR_ACT_POOL, RR_ACT_PRELU, RR_ACT_RES, RR_BF16, RR_F32, RR_CONV1X1, RR_CONV3X3,
-                   RR_CONVT_DOWN, RR_CONVT_UP, RR_DISTORT_KMAX, BnBwdDesc, DistortParam, IgemmDesc, PackJob, WgradDesc, lib)
+                   RR_CONVT_DOWN, RR_CONVT_UP, RR_DISTORT_KMAX, RR_EUNSUPPORTED, BnBwdDesc, DistortParam, IgemmDesc, PackJob, WgradDesc, lib)
 
 __all__ = [
     "rr_dtype", "stream", "pack_conv", "pack_convT", "bias_tile4", "igemm", "wgrad",
@@ -840,19 +840,27 @@ def first_conv_wgrad(col, dy, dw, db):
     return dw, db
 
 
-def first_conv_wgrad_act(x_nchw, dy, t_pre, act, alpha, dw, db, dalpha=None):
+def first_conv_wgrad_act(x_nchw, dy, t_pre, act, alpha, dw, db, dalpha=None, wpack=None):
     """First-conv weight/bias grad fused with its ReLU (act 1) / PReLU (act
-    2) backward, from the NCHW fp32 image (rr_conv_in_wgrad_act)."""
-    _need_cuda(x_nchw, dy, t_pre)
+    2) backward, from the NCHW fp32 image (rr_conv_in_wgrad_act).
+    ``t_pre`` None: the pre-activation was not stored; it is recomputed from
+    ``wpack``, the kpad-32 pack the forward used (rr_conv_in_wgrad_act_rec)
+    -- bitwise the same gradients."""
+    rec = t_pre is None
+    src = wpack if rec else t_pre
+    _need_cuda(x_nchw, dy, src)
     n, cin, h, w = x_nchw.shape
-    if cin != 3 or dy.shape[-1] != 64 or dy.dtype != torch.bfloat16 or t_pre.dtype != torch.bfloat16:
+    if cin != 3 or dy.shape[-1] != 64 or dy.dtype != torch.bfloat16 or src.dtype != torch.bfloat16:
         raise ValueError("rr_conv_in_wgrad_act: 3 -> 64 channels, bf16 grads")
+    if rec and wpack.numel() != 64 * KPAD_MFMA:
+        raise ValueError("rr_conv_in_wgrad_act_rec: the kpad-32 pack of a 3 -> 64 conv")
     L = lib()
     wsb = L.rr_conv_in_wgrad_act_workspace(n, h, w)
     ws = _ws(wsb, dy.device)
-    L.check(L.rr_conv_in_wgrad_act(n, h, w, _p(x_nchw.contiguous()), _p(dy), _p(t_pre), int(act),
-                                   _p(alpha), _p(dw), _p(db), _p(dalpha), _p(ws), wsb, stream()),
-            "rr_conv_in_wgrad_act")
+    fn = L.rr_conv_in_wgrad_act_rec if rec else L.rr_conv_in_wgrad_act
+    L.check(fn(n, h, w, _p(x_nchw.contiguous()), _p(dy), _p(src), int(act), _p(alpha), _p(dw), _p(db),
+               _p(dalpha), _p(ws), wsb, stream()),
+            "rr_conv_in_wgrad_act_rec" if rec else "rr_conv_in_wgrad_act")
     return dw, db
 
 
@@ -939,6 +947,33 @@ def conv_out_bwd(dy_nchw, x, wt, mask_relu=False, want_dx=True, dw=None, db=None
     return dx, dw, db
 
 
+def affine_act_conv_out_ok(x, cout):
+    """rr_affine_act_conv_out / rr_conv_out_bwd_bnred_rec take this tail
+    (``x`` its NHWC pre-BN tensor) and a final conv of ``cout`` channels."""
+    L = lib()
+    return (x.dtype == torch.bfloat16 and x.shape[-1] == 64 and cout == 3 and x.numel() // 64 < 2 ** 31 - 16
+            and hasattr(L, "rr_affine_act_conv_out") and hasattr(L, "rr_conv_out_bwd_bnred_rec"))
+
+
+def affine_act_conv_out(x, scale, shift, res, res_scale, res_shift, wpack, bias, cout, want_y=True):
+    """The BN-shortcut residual tail + the final 1x1 conv in one pass
+    (rr_affine_act_conv_out): -> (y or None, out fp32 NCHW), bitwise
+    ``affine_act(..., relu=True)`` then ``conv_out_fwd(y, ..., wpack=wpack)``.
+    ``want_y=False``: the tail's output is not stored.  None where the library
+    does not take the shape (the caller runs the two passes)."""
+    _need_cuda(x, res, wpack)
+    n, h, w, Cc = x.shape
+    y = torch.empty_like(x) if want_y else None
+    out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
+    rc = lib().rr_affine_act_conv_out(rr_dtype(x.dtype), n, h, w, Cc, cout, _p(x), _p(scale), _p(shift),
+                                      _p(res), _p(res_scale), _p(res_shift), _p(wpack), _p(bias), _p(y),
+                                      _p(out), stream())
+    if rc == RR_EUNSUPPORTED:
+        return None
+    lib().check(rc, "rr_affine_act_conv_out")
+    return y, out
+
+
 def bn_backward_convout(dy_nchw, x, wt, t0, mean0, inv0, gamma0, t1, mean1, inv1, gamma1,
                         recompute, outs, dw, db):
     """The residual-tail BN backward (two BNs, recomputed ReLU mask: as
@@ -948,32 +983,44 @@ def bn_backward_convout(dy_nchw, x, wt, t0, mean0, inv0, gamma0, t1, mean1, inv1
     reduce), rr_bn_bwd_finalize, rr_bn_bwd_apply_convout (g recomputed from
     ``dy_nchw``).  Train mode only.  Returns dict(dt0, dt1); None where the
     library does not take the shape (the caller runs conv_out_bwd +
-    bn_backward)."""
-    n, h, w, Cc = x.shape
+    bn_backward).
+
+    ``x`` None: the block output was never stored (affine_act_conv_out with
+    want_y=False); rr_conv_out_bwd_bnred_rec recomputes it from t0, t1 and
+    ``recompute`` -- bitwise the same gradients."""
+    n, h, w, Cc = t0.shape
     cout = wt.shape[0]
     if Cc != 64 or cout != 3 or not hasattr(lib(), "rr_conv_out_bwd_bnred"):
         return None
+    if x is None and not affine_act_conv_out_ok(t0, cout):
+        raise RuntimeError("bn_backward_convout: no stored block output and no recompute kernel")
     P = n * h * w
-    dev = x.device
-    d = BnBwdDesc(rr_dtype(x.dtype), P, Cc, 4, 2, 0, 0, None, None)
+    dev = t0.device
+    d = BnBwdDesc(rr_dtype(t0.dtype), P, Cc, 4, 2, 0, 0, None, None)
     blocks = lib().rr_bn_bwd_blocks(C.byref(d))
     part = torch.empty(blocks * Cc * 3 + blocks, dtype=torch.float32, device=dev)
     ws = _ws(lib().rr_conv_out_bwd_bnred_workspace(P, Cc, cout), dev)
     dy = dy_nchw.contiguous()
     w2 = wt.reshape(cout, Cc)
     s = stream()
-    lib().check(lib().rr_conv_out_bwd_bnred(C.byref(d), n, h, w, cout, _p(dy), _p(x), _p(w2), _p(t0),
-                                            _p(mean0), _p(inv0), _p(t1), _p(mean1), _p(inv1), _p(dw),
-                                            _p(db), _p(part), _p(ws), ws.numel(), s),
-                "rr_conv_out_bwd_bnred")
+    aff_s, aff_b = (q.contiguous() for q in recompute)
+    if x is None:
+        lib().check(lib().rr_conv_out_bwd_bnred_rec(n, h, w, cout, C.byref(d), _p(dy), _p(w2), _p(aff_s),
+                                                    _p(aff_b), _p(t0), _p(mean0), _p(inv0), _p(t1),
+                                                    _p(mean1), _p(inv1), _p(dw), _p(db), _p(part), _p(ws),
+                                                    ws.numel(), s), "rr_conv_out_bwd_bnred_rec")
+    else:
+        lib().check(lib().rr_conv_out_bwd_bnred(C.byref(d), n, h, w, cout, _p(dy), _p(x), _p(w2), _p(t0),
+                                                _p(mean0), _p(inv0), _p(t1), _p(mean1), _p(inv1), _p(dw),
+                                                _p(db), _p(part), _p(ws), ws.numel(), s),
+                    "rr_conv_out_bwd_bnred")
     coef = torch.empty(Cc * 6, dtype=torch.float32, device=dev)
     lib().check(lib().rr_bn_bwd_finalize(C.byref(d), _p(part), _p(gamma0), _p(inv0), _p(gamma1),
                                          _p(inv1), _p(outs["dgamma0"]), _p(outs["dbeta0"]),
                                          _p(outs["dgamma1"]), _p(outs["dbeta1"]), None, _p(coef), s),
                 "rr_bn_bwd_finalize")
-    aff_s, aff_b = (q.contiguous() for q in recompute)
-    dt0 = torch.empty_like(x)
-    dt1 = torch.empty_like(x)
+    dt0 = torch.empty_like(t0)
+    dt1 = torch.empty_like(t0)
     lib().check(lib().rr_bn_bwd_apply_convout(C.byref(d), h, w, _p(dy), _p(w2), cout, _p(aff_s),
                                               _p(aff_b), _p(t0), _p(mean0), _p(inv0), _p(t1),
                                               _p(mean1), _p(inv1), _p(coef), _p(dt0), _p(dt1), s),

@@ -411,6 +411,37 @@ int rr_bn_bwd_apply_convout(const rr_bnbwd_desc *d, int h, int w, const float *d
                             const float *mean0, const float *invstd0, const void *t1,
                             const float *mean1, const float *invstd1, const float *coef,
                             void *dt0, void *dt1, rr_stream stream);
+/* rr_conv_out_bwd_bnred without the stored block output: x is recomputed per
+ * element from t0 / t1 and the forward affines aff_s / aff_b [2][C] (rows:
+ * BN0, BN1 -- what mask kind 4 reads), x = round(max(t0*aff_s[c] + aff_b[c] +
+ * (t1*aff_s[C+c] + aff_b[C+c]), 0)) in rr_affine_act's own fp32 expression, so
+ * it is bitwise the tensor rr_affine_act / rr_affine_act_conv_out would have
+ * stored, and dw, db, bn_partial and the workspace contents are bitwise
+ * rr_conv_out_bwd_bnred's.  Same workspace (rr_conv_out_bwd_bnred_workspace).
+ * bf16, C = 64, cout = 3; RR_EUNSUPPORTED otherwise, nothing launched (the
+ * caller keeps the stored output and calls rr_conv_out_bwd_bnred).  Replaces
+ * the same autograd as rr_conv_out_bwd_bnred (14:114-115 + 14:149). */
+int rr_conv_out_bwd_bnred_rec(int n, int h, int w, int cout, const rr_bnbwd_desc *d, const float *dy,
+                              const float *wt, const float *aff_s, const float *aff_b, const void *t0,
+                              const float *mean0, const float *invstd0, const void *t1,
+                              const float *mean1, const float *invstd1, float *dw, float *db,
+                              float *bn_partial, void *ws, size_t ws_bytes, rr_stream stream);
+/* The BN-shortcut residual tail and the final 1x1 conv it feeds in one pass
+ * (ResUNet dec1 -> final, 14:114-115 + 14:149), x / res / y NHWC [n][h][w][C]
+ * of element type x_dtype:
+ *   y   = relu(x*scale[c] + shift[c] + (res*res_scale[c] + res_shift[c])),
+ *         bitwise rr_affine_act's; stored only when y != NULL
+ *   out[n][co][h][w] = bias[co] + sum_c y[c] * w[co][c], fp32 NCHW, bitwise
+ *         rr_igemm's (RR_CONV1X1, out_nchw) on the stored y
+ * wpack: the forward pack of the conv's weights (rr_pack_conv, k = 1:
+ * [cout][C]).  With y NULL the block output never reaches memory (the
+ * backward recomputes it: rr_conv_out_bwd_bnred_rec, mask kind 4).
+ * x_dtype RR_BF16, C = 64, cout <= 4; RR_EUNSUPPORTED otherwise, nothing
+ * launched (the caller runs rr_affine_act + rr_igemm). */
+int rr_affine_act_conv_out(int x_dtype, int n, int h, int w, int C, int cout, const void *x,
+                           const float *scale, const float *shift, const void *res,
+                           const float *res_scale, const float *res_shift, const void *wpack,
+                           const float *bias, void *y, float *out, rr_stream stream);
 /* apply: dt_i = coef_a[c]*(gm - coef_b[c] - xhat_i*coef_c[c]); optional gm out */
 int rr_bn_bwd_apply(const rr_bnbwd_desc *d, const void *g, const void *aux,
                     const float *aff_s, const float *aff_b, const float *alpha,
@@ -603,6 +634,17 @@ int rr_conv_in_wgrad_act(int n, int h, int w, const float *x, const void *dy,
                          const void *t_pre, int act, const float *alpha,
                          float *dw, float *db, float *dalpha, void *workspace,
                          size_t workspace_bytes, rr_stream stream);
+/* rr_conv_in_wgrad_act without the stored pre-activation (14:122-123): t is
+ * recomputed per 64-pixel step from the image patch the kernel stages anyway
+ * and wpack32, the kpad-32 pack (rr_pack_conv_in) the forward's
+ * rr_conv_in_mfma read -- the forward's own K = 32 MFMA and bf16 rounding, so
+ * dw, db, dalpha and the workspace contents are bitwise rr_conv_in_wgrad_act's
+ * given the y_pre that forward would have stored (it may then be called with
+ * y_pre NULL).  Same workspace, same arguments otherwise. */
+int rr_conv_in_wgrad_act_rec(int n, int h, int w, const float *x, const void *dy,
+                             const void *wpack32, int act, const float *alpha,
+                             float *dw, float *db, float *dalpha, void *workspace,
+                             size_t workspace_bytes, rr_stream stream);
 int rr_conv_in_dgrad(int dtype, int n, int h, int w, int cin, int cout,
                      const void *dy, const float *wt, float *dx, int accumulate,
                      rr_stream stream);
