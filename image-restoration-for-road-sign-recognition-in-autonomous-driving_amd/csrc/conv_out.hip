@@ -482,7 +482,8 @@ extern "C" size_t rr_conv_out_bwd_workspace(int n, int h, int w, int cin, int co
 extern "C" int rr_conv_out_bwd(int dtype, int n, int h, int w, int cin, int cout, const float *dy,
                                const void *x, const float *wt, void *dx, int mask_relu, float *dw,
                                float *db, void *ws, size_t ws_bytes, rr_stream stream) {
-  if (!dy || !x || !wt || cout > 4 || cout <= 0 || cin > 64) return RR_EINVAL;
+  // cin >= cout: the db row of a partial slab has cin slots and holds cout values
+  if (!dy || !x || !wt || cout > 4 || cout <= 0 || cin > 64 || cin < cout) return RR_EINVAL;
   const int blocks = conv_out_blocks(n, h, w);
   const size_t pbytes = (size_t)blocks * (cout + 1) * cin * sizeof(float);
   if (!ws || ws_bytes < pbytes + rr_colreduce_bytes(blocks, (cout + 1) * cin)) return RR_EWORKSPACE;

@@ -32,6 +32,13 @@ __global__ void prelu_bwd_kernel(long long count, const T *__restrict__ dy, cons
     }
     store4<T>(dx + i * 4, o);
   }
+  // the count % 4 tail: workgroup 0, one element per thread
+  if (blockIdx.x == 0 && (long long)threadIdx.x < count - n4 * 4) {
+    const long long i = n4 * 4 + threadIdx.x;
+    const float d = Elt<T>::load(dy, i), u = Elt<T>::load(yp, i);
+    Elt<T>::store(dx, i, u > 0.f ? d : a * d);
+    s += u > 0.f ? 0.f : d * u;
+  }
   red[threadIdx.x] = s;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -330,7 +337,7 @@ __global__ void argmax_kernel(int n, int k, const float *__restrict__ x, int64_t
 extern "C" int rr_prelu_bwd(int dtype, long long count, const void *dy, const void *y_pre,
                             const float *alpha, void *dx, float *alpha_partial, int blocks,
                             float *dalpha, rr_stream stream) {
-  if (!dy || !y_pre || !alpha || !dx || !alpha_partial || !dalpha || count % 4 || blocks <= 0 ||
+  if (!dy || !y_pre || !alpha || !dx || !alpha_partial || !dalpha || count <= 0 || blocks <= 0 ||
       blocks > 4096)
     return RR_EINVAL;
   hipStream_t st = (hipStream_t)stream;

@@ -650,7 +650,8 @@ int rr_conv_in_dgrad(int dtype, int n, int h, int w, int cin, int cout,
                      rr_stream stream);
 /* PReLU backward on an NHWC tensor (14:122 enc1's PReLU): dx = dy*(y_pre>0 ?
  * 1 : alpha); alpha_partial holds `blocks` per-workgroup partials and the
- * alpha gradient (their fixed-order sum) is written to *dalpha. */
+ * alpha gradient (their fixed-order sum) is written to *dalpha.  Any count
+ * >= 1: workgroup 0 takes the count % 4 elements behind the 4-element vectors. */
 int rr_prelu_bwd(int dtype, long long count, const void *dy, const void *y_pre,
                  const float *alpha, void *dx, float *alpha_partial, int blocks,
                  float *dalpha, rr_stream stream);
@@ -660,7 +661,9 @@ int rr_conv_out_fwd(int dtype, int n, int h, int w, int cin, int cout,
                     const void *x, const float *wt, const float *b, float *y,
                     rr_stream stream);
 /* grads of the last layer: dx (NHWC dtype, optional mask by x>0),
- * dw / db (fp32, need workspace) from dy (NCHW fp32) */
+ * dw / db (fp32, need workspace) from dy (NCHW fp32).  cout <= 4 and
+ * cout <= cin <= 64; RR_EINVAL otherwise, nothing launched (a partial slab's
+ * db row has cin slots for its cout values). */
 int rr_conv_out_bwd(int dtype, int n, int h, int w, int cin, int cout,
                     const float *dy, const void *x, const float *wt,
                     void *dx, int mask_relu, float *dw, float *db, void *ws,

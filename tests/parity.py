@@ -747,3 +747,267 @@ def convout_tail_bounds(dy, wt, keep, t, mean, invstd, gamma, out_dtype, x, n_su
     out["dw"] = _finish(d2.t() @ x2, d2.abs().t() @ x2.abs(), P, torch.float32, 1)
     out["db"] = _finish(d2.sum(0), d2.abs().sum(0), P, torch.float32, 1)
     return out
+
+
+# ---------------------------------------------------------------------------
+# the boundary layers: csrc/conv_in.hip (3 -> 64 from the NCHW fp32 image),
+# csrc/conv_out.hip (64 -> 3 into NCHW fp32) and rr_prelu_bwd
+#
+# Operands.  rr_conv_in_mfma and rr_conv_in_wgrad_act[_rec] multiply the image
+# rounded to bf16 (RNE) with the weights and the bias as the kpad-32 pack
+# holds them (bf16, the bias in column 27 against a patch column of ones): all
+# products are exact in fp32, the forward sums K = 28 of them from a zero
+# accumulator.  The VALU entry points (rr_conv_in_fwd / _wgrad / _dgrad,
+# rr_conv_out_fwd / _bwd) multiply the fp32 image and weights unrounded with
+# activations or grads in T: one rounding per product, inside the 2 K u A.
+#
+# No mask is sign-ambiguous: t and x are given tensors compared with 0
+# exactly; the forward's activations are continuous (1-Lipschitz).
+#
+# The reduce skeleton (as the BN family above): a workgroup sums the terms of
+# its pixel range in fp32 into one partial row, the rows are summed in fp64
+# (rr_colreduce + a finalize) and stored once as fp32 (``cast32``):
+#   n_sum u sum|term|, then cast32,
+# n_sum the number of terms of the longest fp32 sum -- the any-order bound
+# (n - 1) u sum|term| of n terms, plus one u where the products are rounded.
+# The splits below restate each launcher's; the tests assert them against the
+# library's workspace queries (partial rows of ``blocks`` workgroups in fp32 +
+# min(blocks, 64) column-reduce rows in fp64).
+
+def _ceil_div(a, b):
+    return -(-int(a) // int(b))
+
+
+def colreduce_chunks(rows):
+    """rr_colreduce's fp64 rows behind the partial slabs"""
+    return max(1, rows) if rows < 64 else 64
+
+
+def _split_bytes(blocks, cols):
+    return blocks * cols * 4 + colreduce_chunks(blocks) * cols * 8
+
+
+def conv_in_act_split(P):
+    """(workgroups, pixels per workgroup) of rr_conv_in_wgrad_act[_rec]:
+    ceil(P / 512) ranges (2048 at the most) of whole 64-pixel steps"""
+    blocks = max(1, min(2048, _ceil_div(P, 512)))
+    return blocks, _ceil_div(_ceil_div(P, blocks), 64) * 64
+
+
+def conv_in_act_workspace(P):
+    """rr_conv_in_wgrad_act_workspace: slabs of [64][32] + a dalpha row of 32"""
+    return _split_bytes(conv_in_act_split(P)[0], 64 * 32 + 32)
+
+
+def conv_in_wgrad_split(P):
+    """rr_conv_in_wgrad: ceil(P / 2048) ranges, 1024 at the most"""
+    blocks = max(1, min(1024, _ceil_div(P, 2048)))
+    return blocks, _ceil_div(P, blocks)
+
+
+def conv_in_wgrad_workspace(P, cout):
+    return _split_bytes(conv_in_wgrad_split(P)[0], cout * 32)
+
+
+def conv_out_split(P):
+    """rr_conv_out_bwd: ceil(P / 1024) ranges, 2048 at the most"""
+    blocks = max(1, min(2048, _ceil_div(P, 1024)))
+    return blocks, _ceil_div(P, blocks)
+
+
+def conv_out_workspace(P, cin, cout):
+    """slabs of cout dw rows + one db row, cin slots each"""
+    return _split_bytes(conv_out_split(P)[0], (cout + 1) * cin)
+
+
+def conv_out_db_row_holds(cin, cout):
+    """the db row of a slab [(cout + 1)][cin] has cin slots for cout values:
+    with cin < cout, value co >= cin of workgroup b lands at slab offset
+    (cout + 1) cin + (co - cin) -- the next workgroup's slab, or, for the last
+    workgroup, the column-reduce rows behind the slabs"""
+    return cout <= cin
+
+
+def prelu_bwd_chain(count, blocks):
+    """terms of the longest per-thread fp32 chain of rr_prelu_bwd: 4 per
+    grid-stride trip over the count / 4 vectors, 1 more for the count % 4 tail"""
+    return 4 * _ceil_div(max(count // 4, 1), blocks * 256) + 1
+
+
+def bf16r(t):
+    """t rounded to bf16 (RNE), fp64"""
+    return t.float().to(torch.bfloat16).double()
+
+
+def patches3(x, kpad=None):
+    """the 3x3 patch rows [P, 9 cin + 1] (or kpad columns) of x [n, cin, h, w],
+    fp64: column j = ci 9 + ky 3 + kx holds x[n, ci, y + ky - 1, x + kx - 1] (0
+    outside the image), column 9 cin holds 1, the rest 0 -- rr_im2col3's layout"""
+    x = x.double()
+    n, cin, h, w = x.shape
+    col = F.unfold(x, 3, padding=1).permute(0, 2, 1).reshape(n * h * w, 9 * cin)
+    out = torch.zeros(n * h * w, 9 * cin + 1 if kpad is None else kpad, dtype=torch.float64)
+    out[:, :9 * cin] = col
+    out[:, 9 * cin] = 1.0
+    return out
+
+
+def conv_in_pack(wt, b, kpad, dtype):
+    """rr_pack_conv_in's [cout][kpad] in ``dtype`` (as fp32): the weights
+    [cout][cin 9], the bias in column 9 cin, zeros up to kpad"""
+    cout, kk = wt.shape[0], wt.shape[1] * 9
+    out = torch.zeros(cout, kpad)
+    out[:, :kk] = wt.reshape(cout, kk)
+    if b is not None:
+        out[:, kk] = b
+    return out.to(dtype).float()
+
+
+def conv_in_mfma_bounds(x, wt, b, act, alpha):
+    """rr_conv_in_mfma of x [n, 3, h, w] fp32, wt [64, 3, 3, 3], b [64]: {pre,
+    act: (ref64, bound64)} NHWC.  Operands: bf16(x), the bf16 kpad-32 pack; K =
+    28 exact products from a zero accumulator (2 K u A); y_pre and y_act are
+    each ONE bf16 store of the fp32 accumulator v (y_act = PReLU(v), not of
+    the rounded y_pre: the slope's fp32 product adds u |alpha v|; act 0 and
+    ReLU add nothing)."""
+    n, _, h, w = x.shape
+    pt = patches3(bf16r(x), 32)
+    pack = conv_in_pack(wt, b, 32, torch.bfloat16).double()
+    ref = (pt @ pack.t()).reshape(n, h, w, -1)
+    e = 2.0 * 28 * U * (pt.abs() @ pack.abs().t()).reshape(n, h, w, -1)
+    out = {"pre": (ref, _stored(ref, e, torch.bfloat16))}
+    if act == 0:
+        ra, ea = ref, e
+    elif act == 1:
+        ra, ea = ref.clamp_min(0), e
+    else:
+        assert abs(alpha) <= 1
+        ra = torch.where(ref > 0, ref, alpha * ref)
+        ea = e + U * ra.abs()
+    out["act"] = (ra, _stored(ra, ea, torch.bfloat16))
+    return out
+
+
+def conv_in_gp(g, t, act, alpha):
+    """gp = bf16(t > 0 ? g : fp32(alpha g)) (ReLU: alpha = 0) of g, t NHWC
+    bf16-exact: the operand of the fused weight grad, reproduced bit for bit"""
+    g32, t32 = g.float(), t.float()
+    al = torch.tensor(float(alpha) if act == 2 else 0.0, dtype=torch.float32)
+    return torch.where(t32 > 0, g32, al * g32).to(torch.bfloat16).double()
+
+
+def conv_in_wgrad_act_bounds(x, g, t, act, alpha):
+    """rr_conv_in_wgrad_act[_rec]: {dw [64, 27], db [64], dalpha 0-d}.
+    dW[co][j] = sum_p gp[p, co] patch[p, j] of gp (``conv_in_gp``) and the bf16
+    patch rows with their ones column (db): exact products, one MFMA
+    accumulator per workgroup over its <= ppb pixels (n_sum = ppb), fp64
+    across, one fp32 store.  dalpha = sum_{t <= 0} g t: g t exact in fp32 (8 x
+    8 bits); a thread adds its 2 pixels x 8 channels of each 64-pixel step in
+    one chain (16 ppb / 64 terms), a 256-wide LDS tree adds 8 levels: no term
+    is touched by more than ppb / 4 + 8 fp32 adds; fp64 across, one store."""
+    P = g.numel() // 64
+    _, ppb = conv_in_act_split(P)
+    gp = conv_in_gp(g, t, act, alpha).reshape(P, 64)
+    pt = patches3(bf16r(x), 28)
+    ref, S = gp.t() @ pt, gp.abs().t() @ pt.abs()
+    r, bd = cast32((ref, ppb * U * S))
+    out = {"dw": (r[:, :27].contiguous(), bd[:, :27].contiguous()), "db": (r[:, 27].contiguous(), bd[:, 27].contiguous())}
+    term = torch.where(t.double() > 0, _Z, g.double() * t.double())
+    out["dalpha"] = cast32((term.sum(), (ppb // 4 + 8) * U * term.abs().sum()))
+    return out
+
+
+def conv_in_wgrad_bounds(x, dy):
+    """rr_conv_in_wgrad (VALU) of x [n, cin, h, w] fp32 unrounded and dy [n, h,
+    w, cout] in T: (ref64, bound64) [cout, 9 cin + 1], the bias grad in the
+    last column.  64-term fp32 stage sums (64 rounded products in one chain:
+    64 u), folded into fp64, ONE fp32 store per workgroup (u of its partial),
+    one more u for the second order and the fp64 folds: 66 u sum|term|; fp64
+    across workgroups, one store (``cast32``)."""
+    cout = dy.shape[-1]
+    pt = patches3(x)
+    d = dy.double().reshape(-1, cout)
+    return cast32((d.t() @ pt, 66 * U * (d.abs().t() @ pt.abs())))
+
+
+def conv_in_dgrad_bounds(dy, wt, dx0=None):
+    """rr_conv_in_dgrad (and the packed image-grad route): dy [n, cout, h, w]
+    (NCHW here), wt [cout, cin, 3, 3] -> the image grad, NHWC for
+    ``assert_within(nchw=True)``; K = 9 cout (+ 1 accumulated into dx0, NCHW)"""
+    dy, wt = dy.double(), wt.double()
+    ref = _nhwc(F.conv_transpose2d(dy, wt, padding=1))
+    A = _nhwc(F.conv_transpose2d(dy.abs(), wt.abs(), padding=1))
+    return epilogue_bound((ref, A), 9 * wt.shape[0], None, torch.float32, extra=dx0)
+
+
+def conv_out_bwd_bounds(dy, x, wt, mask_relu, dtype):
+    """rr_conv_out_bwd of dy [n, cout, h, w] fp32, x [n, h, w, cin] in T, wt
+    [cout, cin] fp32: dx = sum_co dy w (K = cout fp32 products), masked by x >
+    0 (a tensor of its own), one store; dw [cout, cin] = sum_p dy x and db =
+    sum_p dy: one fp32 sum of <= ppb rounded products per workgroup (n_sum =
+    ppb, ``conv_out_split``), fp64 across, one store."""
+    cout, cin = wt.shape
+    d = dy.double().permute(0, 2, 3, 1).contiguous()
+    w64, x64 = wt.double(), x.double()
+    dx = _finish(d @ w64, d.abs() @ w64.abs(), cout, dtype, 1)
+    if mask_relu:
+        dx = (torch.where(x64 > 0, dx[0], _Z), dx[1])
+    P = x64.numel() // cin
+    _, ppb = conv_out_split(P)
+    d2, x2 = d.reshape(P, cout), x64.reshape(P, cin)
+    return {"dx": dx, "dw": cast32((d2.t() @ x2, ppb * U * (d2.abs().t() @ x2.abs()))),
+            "db": cast32((d2.sum(0), ppb * U * d2.abs().sum(0)))}
+
+
+def conv1x1_nchw_bound(y, wq, bias):
+    """out [n, h, w, cout] (for ``assert_within(nchw=True)``) = bias + y w of
+    y [n, h, w, c] and wq [cout, c] as stored: K = c + 1"""
+    y, wq, bias = y.double(), wq.double(), bias.double()
+    return _finish(y @ wq.t() + bias, y.abs() @ wq.abs().t() + bias.abs(), wq.shape[1] + 1, torch.float32, 1)
+
+
+def prelu_bwd_bounds(dy, t, alpha, dtype, blocks):
+    """rr_prelu_bwd of flat dy, t in T: dx = t > 0 ? dy : alpha dy, one fp32
+    product (u |alpha dy|), one store; dalpha = sum_{t <= 0} dy t: a product
+    (exact in bf16, one rounding in fp32), a per-thread chain of
+    ``prelu_bwd_chain`` terms and a 256-wide tree (8 levels) per workgroup,
+    fp64 across the ``blocks`` partials, one store."""
+    assert abs(alpha) <= 1
+    d, t = dy.double(), t.double()
+    ref = torch.where(t > 0, d, alpha * d)
+    dx = (ref, _stored(ref, torch.where(t > 0, _Z, U * ref.abs()), dtype))
+    term = torch.where(t > 0, _Z, d * t)
+    n_sum = prelu_bwd_chain(d.numel(), blocks) + 8 + (0 if dtype == torch.bfloat16 else 1)
+    return {"dx": dx, "dalpha": cast32((term.sum(), n_sum * U * term.abs().sum()))}
+
+
+# ---------------------------------------------------------------------------
+# shared inputs of the boundary tests
+
+def with_zeros(t, seed, share=0.02):
+    """t with about ``share`` of its elements set to an exact 0, half of them
+    to -0.0: what a mask written as ``>= 0`` instead of ``> 0`` gets wrong (a
+    ReLU output, the x of the last conv's backward, is full of them)"""
+    g = torch.Generator().manual_seed(seed)
+    r = torch.rand(t.shape, generator=g)
+    t = torch.where(r < share, torch.zeros(()), t)
+    return torch.where(r < share / 2, torch.full((), -0.0), t)
+
+
+TAIL_SHAPES = [(3, 5, 7), (2, 8, 8), (1, 16, 24)]
+_TAIL = {}
+
+
+def tail_inputs(shape):
+    """one set of host inputs of the residual tail + final 1x1 conv per shape,
+    shared by the tests and left unchanged"""
+    if shape not in _TAIL:
+        def rnd(*sh, seed):
+            return torch.randn(*sh, generator=torch.Generator().manual_seed(seed))
+        n, h, w = shape
+        sc = [rnd(64, seed=3) * 0.7, rnd(64, seed=4) * 0.7]          # about half the scales negative
+        _TAIL[shape] = dict(t2=rnd(n, h, w, 64, seed=1).to(torch.bfloat16), s=rnd(n, h, w, 64, seed=2).to(torch.bfloat16),
+                            sc=sc, sh=[rnd(64, seed=5) * 0.3, rnd(64, seed=6) * 0.3],
+                            wt=rnd(3, 64, 1, 1, seed=7) / 8.0, bias=rnd(3, seed=8))
+        assert all(int((v < 0).sum()) >= 8 for v in sc)
+    return _TAIL[shape]

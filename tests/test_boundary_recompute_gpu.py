@@ -17,6 +17,7 @@ import ctypes as C
 import pytest
 import torch
 
+from parity import TAIL_SHAPES, tail_inputs as _tail_inputs
 from rrpath import set_path
 
 pytestmark = pytest.mark.gpu
@@ -39,24 +40,6 @@ def bits(t):
 
 def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
-
-
-_TAIL = {}
-
-
-def _tail_inputs(shape):
-    """one set of host inputs per shape, shared by the tests and left unchanged"""
-    if shape not in _TAIL:
-        n, h, w = shape
-        sc = [rnd(64, seed=3) * 0.7, rnd(64, seed=4) * 0.7]          # about half the scales negative
-        _TAIL[shape] = dict(t2=rnd(n, h, w, 64, seed=1).to(BF), s=rnd(n, h, w, 64, seed=2).to(BF),
-                            sc=sc, sh=[rnd(64, seed=5) * 0.3, rnd(64, seed=6) * 0.3],
-                            wt=rnd(3, 64, 1, 1, seed=7) / 8.0, bias=rnd(3, seed=8))
-        assert all(int((v < 0).sum()) >= 8 for v in sc)
-    return _TAIL[shape]
-
-
-TAIL_SHAPES = [(3, 5, 7), (2, 8, 8), (1, 16, 24)]
 
 
 # (the streaming 1x1 takes whole 16-pixel blocks only: not P = 105)

@@ -1,7 +1,9 @@
 """Per-element parity and guard bands for every convolution family: tap-reuse
 conv3r (whole-row and row-segment tiles, 4- and 8-wave workgroups), the
 row-streaming stream3 (whole rows and column strips), stream1 (1x1, convT),
-the LDS-halo and tiled implicit GEMM, and the weight grads.
+the LDS-halo and tiled implicit GEMM (with the image grad, c_out = 3 into NCHW
+fp32: the narrow 16-column halo tile one-shot and persistent, and the tiled
+kernel where it is not eligible), and the weight grads.
 
 Every case forces its family with RR_PATH, asserts the kernel instance the
 library will launch, and calls the C ABI directly on buffers of its own:
@@ -28,6 +30,7 @@ element of theirs is held to a derived bound in
 tests/test_fused_elementwise_gpu.py."""
 import ctypes as C
 import math
+import os
 
 import pytest
 import torch
@@ -57,6 +60,8 @@ EPI = {
     "pool": (1 | 8, 0, 1, 0, 0, 0),
     "pool_only": (1 | 8 | 16, 0, 1, 0, 0, 0),
     "nchw": (0, 0, 1, 0, 0, 1),
+    "nchw_plain": (0, 0, 0, 0, 0, 1),
+    "nchw_acc": (0, 1, 0, 0, 0, 1),
 }
 LOAD = ["plain", "bias_relu", "bias_stats", "acc", "mask", "acc_mask"]
 EX = ["prelu", "res_relu", "pool", "pool_only"]
@@ -67,6 +72,7 @@ W4, W8 = "stream3=0,conv3r_wg=4", "stream3=0,conv3r_wg=8"
 SEG, SEG4, SEG8 = "stream3=0", "stream3=0,conv3r_segwg=4", "stream3=0,conv3r_segwg=8"
 S1 = "stream1_minp=1024"
 TILED = "conv3r=0,stream3=0"
+IMG = ["nchw_plain", "nchw_acc"]      # the image grad: 64 -> 3 into NCHW fp32, K = 576 (+ 1 accumulated into)
 
 # (RR_PATH, dtype, mode, (n, h, w, c_in1, c_in2, c_out), kernel instance, epilogues)
 # modes: 0 3x3, 1 1x1, 2 convT up (c_out = 4 * channels), 3 convT down
@@ -135,6 +141,25 @@ CASES = [
     (TILED, BF, 0, (2, 8, 8, 64, 0, 64), "igemm_kernel<bf16,64,128,m0>", LOAD + ["nchw"]),
     (TILED, BF, 0, (2, 16, 16, 64, 0, 256), "igemm3_halo_kernel<64,16>", LOAD + ["split"]),
     (TILED + ",igemm_halo=0", BF, 0, (2, 16, 16, 64, 0, 256), "igemm_kernel<bf16,64,128,m0>", ["bias_stats", "acc_mask"]),
+    # ---- the image grad (c_out = 3, NCHW fp32): the narrow 16-column halo tile, one launch of one 256-pixel
+    # tile per workgroup at the smallest eligible shape of each width ...
+    ("", BF, 0, (4, 8, 8, 64, 0, 3), "igemm3_halo_kernel<16,8>", IMG),
+    ("", BF, 0, (1, 16, 16, 64, 0, 3), "igemm3_halo_kernel<16,16>", IMG),
+    ("", BF, 0, (1, 8, 32, 64, 0, 3), "igemm3_halo_kernel<16,32>", IMG),
+    ("", BF, 0, (1, 8, 64, 64, 0, 3), "igemm3_halo_kernel<16,64>", IMG),
+    # ... and persistent: past 512 tiles the launcher starts 512 workgroups that walk tiles b, b + 512, ... with
+    # the next tile's halo held in registers (513, 516, 528, 528 tiles: workgroups with 2 tiles and with 1);
+    # 65 x 64 x 64 = 1040 tiles: workgroups get 3 or 2.  The NaN interior catches a tile never written, the
+    # accumulate form's fill one accumulated twice.
+    ("", BF, 0, (2052, 8, 8, 64, 0, 3), "igemm3_halo_kernel<16,8>", IMG),
+    ("", BF, 0, (516, 16, 16, 64, 0, 3), "igemm3_halo_kernel<16,16>", IMG),
+    ("", BF, 0, (132, 32, 32, 64, 0, 3), "igemm3_halo_kernel<16,32>", IMG),
+    ("", BF, 0, (33, 64, 64, 64, 0, 3), "igemm3_halo_kernel<16,64>", IMG),
+    ("", BF, 0, (65, 64, 64, 64, 0, 3), "igemm3_halo_kernel<16,64>", IMG),
+    # the tiled kernel where the halo route is not eligible (odd sizes, a height no multiple of 8, a width of 112)
+    ("", BF, 0, (1, 5, 7, 64, 0, 3), "igemm_kernel<bf16,64,128,m0>", IMG),
+    ("", BF, 0, (3, 40, 16, 64, 0, 3), "igemm_kernel<bf16,64,128,m0>", IMG),
+    ("", BF, 0, (1, 20, 112, 64, 0, 3), "igemm_kernel<bf16,64,128,m0>", IMG),
 ]
 
 
@@ -282,7 +307,7 @@ def test_conv_elementwise(dev, case, epi, monkeypatch):
         outs["y1"] = parity.guarded((on, oh, ow, split), dt, dev)
         outs["y2"] = parity.guarded((on, oh, ow, oc - split), dt, dev)
     elif nchw:
-        outs["y1"] = parity.guarded((on, oc, oh, ow), F32, dev)
+        outs["y1"] = parity.guarded((on, oc, oh, ow), F32, dev, fill=d["y0"] if acc else None)
     elif not act & 16:
         outs["y1"] = parity.guarded(oshape, dt, dev, fill=y0h if acc else None)
     if act & 8:
@@ -315,6 +340,8 @@ def test_conv_elementwise(dev, case, epi, monkeypatch):
         parity.assert_within(outs["y2"][1], ref[..., split:].contiguous(), bound[..., split:].contiguous(), what + " y2")
     elif "y1" in outs:
         parity.assert_within(outs["y1"][1], ref, bound, what, nchw=bool(nchw))
+        if epi in IMG and os.environ.get("RR_PARITY_REPORT"):     # a measurement for DESIGN section 4's table, never asserted
+            print("RATIO %s %s %.3g" % (name, epi, parity.worst_ratio(outs["y1"][1].permute(0, 2, 3, 1), ref, bound)))
     if act & 8:
         yp = outs["pool"][1]
         parity.assert_within(yp, *parity.pooled((ref, bound)), what + " pooled")

@@ -772,3 +772,385 @@ def test_ideal_convout_tail_inside_bounds_and_wrong_image_rejected(dt):
     bad = _rejected(_emulate_convout(d, dt, "the convout dy of image 1 read from image 0"), {k: bounds[k] for k in keys})
     print(f"dy of image 1 read from image 0: rejected by {bad}")
     assert "dt0" in bad and "dw" in bad
+
+
+# ---------------------------------------------------------------------------
+# The boundary layers (csrc/conv_in.hip, csrc/conv_out.hip, rr_prelu_bwd):
+# each helper's ideal kernel -- the stated operand rounding, the launcher's
+# ranges, a SHUFFLED summation order inside a range in fp32, fp64 across
+# ranges, the stated stores -- inside its bound in both dtypes, and the broken
+# kernels of the hand-written border / image-crossing / partial-step
+# arithmetic rejected, with the score each gets under the older checks.
+
+def _shuffle(n, seed):
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))
+
+
+def _patch_rows(xq, img, y, xx, lo=None):
+    """[len, 28] fp32 patch rows (27 taps + the ones column) of pixels (img, y,
+    xx) of xq [n, 3, h, w]; ``lo``: (flat pixel index of each row, first pixel
+    of the range) -- taps whose source pixel lies before the range read 0"""
+    n, _, h, w = xq.shape
+    xp = F.pad(xq, (1, 1, 1, 1))
+    j = torch.arange(27)
+    ci, ky, kx = j // 9, (j % 9) // 3, j % 3
+    v = xp[img[:, None], ci[None, :], y[:, None] + ky[None, :], xx[:, None] + kx[None, :]]
+    if lo is not None:
+        p, p0 = lo
+        src = p[:, None] + (ky[None, :] - 1) * w + (kx[None, :] - 1)
+        v = torch.where(src < p0, torch.zeros(()), v)
+    return torch.cat((v, torch.ones(len(img), 1)), 1)
+
+
+def _pix(P, h, w):
+    p = torch.arange(P)
+    return p, p // (h * w), (p % (h * w)) // w, p % w
+
+
+def _emu_conv_in_mfma(x, wt, b, act, alpha, mutation=None):
+    """rr_conv_in_mfma as the ideal kernel (mutation None): bf16(x) patches,
+    the bf16 pack, the K = 32 sum in fp32 in a shuffled order, y_pre and
+    y_act each one bf16 store of the accumulator -> (pre, act) NHWC"""
+    n, _, h, w = x.shape
+    P = n * h * w
+    xq = x.to(BF).float()
+    p, img, y, xx = _pix(P, h, w)
+    pt = torch.zeros(P, 32)
+    pt[:, :28] = _patch_rows(xq, img, y, xx)
+    if mutation == "left border reads the previous row":
+        # no x check on the left: tap (ky, 0) of column 0 reads flat offset rem + (ky - 1) w - 1 of the plane
+        flat = xq.reshape(n, 3, h * w)
+        rem = p % (h * w)
+        for ci in range(3):
+            for ky in range(3):
+                src = rem + (ky - 1) * w - 1
+                ok = (xx == 0) & (src >= 0) & (src < h * w) & (y + ky - 1 >= 0) & (y + ky - 1 < h)
+                pt[ok, ci * 9 + ky * 3] = flat[img[ok], ci, src[ok]]
+    if mutation == "no bias on the last partial wave" and P % 64:
+        pt[P - P % 64:, 27] = 0.0
+    pack = parity.conv_in_pack(wt, b, 32, BF)
+    perm = _shuffle(32, 5)
+    acc = pt[:, perm] @ pack[:, perm].t()
+    a32 = torch.tensor(0.0 if alpha is None else alpha)
+    ya = {0: acc, 1: acc.clamp_min(0), 2: torch.where(acc > 0, acc, a32 * acc)}[act]
+    return acc.to(BF).reshape(n, h, w, 64), ya.to(BF).reshape(n, h, w, 64)
+
+
+def _first_case(shape, zeros=False):
+    n, h, w = shape
+    x = rnd(n, 3, h, w, seed=21) * 0.5 + 0.3
+    wt, b = rnd(64, 3, 3, 3, seed=22) / 3.0, rnd(64, seed=23) * 0.2
+    g, t = rnd(n, h, w, 64, seed=24).to(BF).float(), rnd(n, h, w, 64, seed=25).to(BF).float()
+    if zeros:
+        t = torch.where(torch.rand(t.shape, generator=torch.Generator().manual_seed(26)) < 0.02, torch.zeros(()), t)
+    return x, wt, b, g, t
+
+
+@pytest.mark.parametrize("shape", [(1, 5, 7), (3, 9, 11), (2, 1, 70), (2, 70, 1)])
+def test_ideal_conv_in_mfma_inside_bound_and_broken_rejected(shape):
+    x, wt, b, _, _ = _first_case(shape)
+    for act, alpha in ((0, None), (1, None), (2, 0.25), (2, 0.0), (2, float(torch.tensor(-0.1)))):
+        rb = parity.conv_in_mfma_bounds(x, wt, b, act, alpha)
+        pre, ya = _emu_conv_in_mfma(x, wt, b, act, alpha)
+        parity.assert_within(pre, *rb["pre"], "ideal y_pre")
+        parity.assert_within(ya, *rb["act"], "ideal y_act")
+        print(f"conv_in_mfma {shape} act {act}: ideal uses {parity.worst_ratio(pre, *rb['pre']):.3f} (pre)"
+              f" {parity.worst_ratio(ya, *rb['act']):.3f} (act) of the bound")
+    rb = parity.conv_in_mfma_bounds(x, wt, b, 2, 0.25)
+    muts = ["left border reads the previous row"] if shape[1] > 1 and shape[2] > 1 else []   # (a previous row to read)
+    muts += ["no bias on the last partial wave"] if (shape[0] * shape[1] * shape[2]) % 64 else []
+    for m in muts:
+        pre, ya = _emu_conv_in_mfma(x, wt, b, 2, 0.25, mutation=m)
+        for got, key in ((pre, "pre"), (ya, "act")):
+            with pytest.raises(AssertionError):
+                parity.assert_within(got, *rb[key], m)
+        print(f"conv_in_mfma {shape} '{m}': relative L2 {rel(pre, rb['pre'][0]):.2e} (pre) {rel(ya, rb['act'][0]):.2e} (act);"
+              " the older check asserts < 4e-3")
+
+
+def _emu_wgrad_act(x, g, t, act, alpha, mutation=None):
+    """rr_conv_in_wgrad_act as the ideal kernel: gp bit for bit, bf16 patches,
+    one fp32 accumulator per range of ``conv_in_act_split`` over its pixels in
+    a shuffled order, fp64 across, one fp32 store -> (dw, db, dalpha)"""
+    n, _, h, w = x.shape
+    P = n * h * w
+    blocks, ppb = parity.conv_in_act_split(P)
+    xq = x.to(BF).float()
+    a32 = torch.tensor(alpha if act == 2 else 0.0)
+    g2, t2 = g.reshape(P, 64), t.reshape(P, 64)
+    keep = (t2 >= 0) if mutation == "mask t >= 0" else (t2 > 0)
+    gp = torch.where(keep, g2, a32 * g2).to(BF).float()
+    term = torch.where(keep, torch.zeros(()), g2 * t2)
+    p, img, y, xx = _pix(P, h, w)
+    slab = torch.zeros(blocks, 64, 28, dtype=torch.float64)
+    arow = torch.zeros(blocks, dtype=torch.float64)
+    for bk in range(blocks):
+        p0, p1 = bk * ppb, min(P, (bk + 1) * ppb)
+        if p0 >= p1:
+            continue
+        i = img[p0:p1].clone()
+        if mutation == "first image's index for a whole step":
+            for q0 in range(p0, p1, 64):
+                i[q0 - p0:q0 - p0 + 64] = img[q0]
+        lo = (p[p0:p1], p0) if mutation == "no reach back across the split" else None
+        pt = _patch_rows(xq, i, y[p0:p1], xx[p0:p1], lo).to(BF).float()
+        perm = _shuffle(p1 - p0, 7 + bk)
+        acc = gp[p0:p1][perm].t() @ pt[perm]
+        if mutation == "dead pixels count in the ones row":
+            # the clamped load's g (pixel p0) not zeroed and a 1 in the ones row for the dead pixels of the last step
+            acc[:, 27] += (-(p1 - p0) % 64) * gp[p0]
+        slab[bk] = acc.double()
+        arow[bk] = term[p0:p1].reshape(-1)[_shuffle((p1 - p0) * 64, 9 + bk)].sum().double()
+    tot = slab.sum(0).float()
+    return tot[:, :27].contiguous(), tot[:, 27].contiguous(), arow.sum().float()
+
+
+WACT_MUTATIONS = {
+    "first image's index for a whole step": (3, 6, 8),       # P = 144: the steps 0..63 and 64..127 each span two images
+    "dead pixels count in the ones row": (3, 6, 8),          # the last step, 128..191, has 48 dead pixels
+    "mask t >= 0": (1, 5, 7),
+    "no reach back across the split": (1, 24, 40),           # ranges of 512 and 448, split inside row 12
+}
+
+
+@pytest.mark.parametrize("shape", [(1, 5, 7), (3, 6, 8), (2, 16, 24), (1, 24, 40), (1, 17, 241), (2, 1, 70), (2, 70, 1)])
+def test_ideal_conv_in_wgrad_act_inside_bounds(shape):
+    x, wt, b, g, t = _first_case(shape, zeros=True)
+    for act, alpha in ((1, 0.0), (2, 0.25), (2, float(torch.tensor(-0.1)))):
+        rb = parity.conv_in_wgrad_act_bounds(x, g, t, act, alpha)
+        dw, db, da = _emu_wgrad_act(x, g, t, act, alpha)
+        parity.assert_within(dw, *rb["dw"], "ideal dw")
+        parity.assert_within(db, *rb["db"], "ideal db")
+        parity.assert_within(da, *rb["dalpha"], "ideal dalpha")
+        print(f"conv_in_wgrad_act {shape} act {act}: ideal uses {parity.worst_ratio(dw, *rb['dw']):.3f} (dw)"
+              f" {parity.worst_ratio(db, *rb['db']):.3f} (db) {parity.worst_ratio(da, *rb['dalpha']):.3f} (dalpha)")
+
+
+@pytest.mark.parametrize("mutation", list(WACT_MUTATIONS))
+def test_broken_conv_in_wgrad_act_rejected(mutation):
+    """dead pixels: their g is zeroed by the kernel, so a 1 in the ones row
+    alone would add 0; the broken kernel here also keeps the g the clamped
+    load brought (pixel p0's), which is what the zeroing and the live-only 1
+    together rule out"""
+    shape = WACT_MUTATIONS[mutation]
+    x, wt, b, g, t = _first_case(shape, zeros=True)
+    rb = parity.conv_in_wgrad_act_bounds(x, g, t, 2, 0.25)
+    dw, db, da = _emu_wgrad_act(x, g, t, 2, 0.25, mutation=mutation)
+    bad = 0
+    for got, key in ((dw, "dw"), (db, "db"), (da, "dalpha")):
+        try:
+            parity.assert_within(got, *rb[key], mutation)
+        except AssertionError:
+            bad += 1
+    assert bad >= 1, mutation
+    old = float((dw.double() - rb["dw"][0]).abs().max() / rb["dw"][0].abs().max())
+    print(f"'{mutation}' {shape}: relative L2 {rel(dw, rb['dw'][0]):.2e} (dw) {rel(db, rb['db'][0]):.2e} (db);"
+          f" max error / max|dw| {old:.2e} (the older check asserts <= 2e-4)")
+
+
+@pytest.mark.parametrize("dt", [BF, F32], ids=["bf16", "f32"])
+def test_ideal_conv_in_valu_kernels_inside_bounds(dt):
+    """rr_conv_in_fwd, rr_conv_in_wgrad (64-pixel fp32 stages in a shuffled
+    order, folded in fp64, one fp32 store per range of 2048, fp64 across),
+    rr_conv_in_dgrad and rr_conv_out_fwd"""
+    n, cin, h, w, cout = 1, 3, 41, 53, 12
+    P = n * h * w
+    x = rnd(n, cin, h, w, seed=51) * 0.5 + 0.3
+    wt, b = rnd(cout, cin, 3, 3, seed=32) / 5.0, rnd(cout, seed=33) * 0.2
+    acc = F.conv2d(x, wt, b, padding=1)
+    for act, f in ((0, lambda v: v), (1, F.relu), (2, lambda v: torch.where(v > 0, v, 0.25 * v))):
+        rb = parity.conv_bound(x, wt, b, 1, dt)
+        rb = {0: rb, 1: parity.relu(rb), 2: parity.prelu(rb, 0.25)}[act]
+        parity.assert_within(nhwc(f(acc).to(dt)), *rb, "ideal rr_conv_in_fwd")
+    dy = rnd(n, h, w, cout, seed=52).to(dt).float()
+    ref, bound = parity.conv_in_wgrad_bounds(x, dy)
+    blocks, ppb = parity.conv_in_wgrad_split(P)
+    assert (blocks, ppb) == (2, 1087)
+    pt = parity.patches3(x).float()
+    d2 = dy.reshape(P, cout)
+    tot = torch.zeros(cout, 28, dtype=torch.float64)
+    for bk in range(blocks):
+        a64 = torch.zeros(cout, 28, dtype=torch.float64)
+        for p0 in range(bk * ppb, min(P, (bk + 1) * ppb), 64):
+            p1 = min(P, (bk + 1) * ppb, p0 + 64)
+            perm = _shuffle(p1 - p0, p0)
+            a64 += (d2[p0:p1][perm].t() @ pt[p0:p1][perm]).double()
+        tot += a64.float().double()
+    parity.assert_within(tot.float(), ref, bound, "ideal rr_conv_in_wgrad")
+    print(f"conv_in_wgrad {dt}: ideal uses {parity.worst_ratio(tot.float(), ref, bound):.3f} of the bound")
+    # the image grad and the last conv's forward: one fp32 sum, one store
+    g = rnd(2, 64, 12, 8, seed=61).to(dt).float()
+    wg = rnd(64, 3, 3, 3, seed=62) / 24.0
+    dx0 = rnd(2, 3, 12, 8, seed=63)
+    parity.assert_within(F.conv_transpose2d(g, wg, padding=1), *parity.conv_in_dgrad_bounds(g, wg), "ideal dgrad", nchw=True)
+    parity.assert_within(F.conv_transpose2d(g, wg, padding=1) + dx0, *parity.conv_in_dgrad_bounds(g, wg, dx0),
+                         "ideal dgrad, accumulate", nchw=True)
+    xo = rnd(3, 12, 9, 11, seed=71).to(dt).float()
+    wo, bo = rnd(3, 12, 1, 1, seed=72) / 12 ** 0.5, rnd(3, seed=73)
+    parity.assert_within(F.conv2d(xo, wo, bo), *parity.conv1x1_bound(xo, wo, bo, F32), "ideal rr_conv_out_fwd", nchw=True)
+    y = rnd(2, 8, 8, 64, seed=74).to(BF).float()
+    wq = (rnd(3, 64, seed=75) / 8.0).to(BF).float()
+    parity.assert_within((y.reshape(-1, 64) @ wq.t() + bo).reshape(2, 8, 8, 3).permute(0, 3, 1, 2),
+                         *parity.conv1x1_nchw_bound(y, wq, bo), "ideal tail 1x1", nchw=True)
+
+
+def _emu_image_grad(g, wt, base, G, mutation=None):
+    """the persistent image-grad walk: 256-pixel tiles, G workgroups, workgroup
+    b takes tiles b, b + G, ...; the ideal tile is the fp32 transposed conv
+    (+ base when accumulating); NaN where nothing is written"""
+    n, _, h, w = g.shape
+    full = F.conv_transpose2d(g, wt, padding=1).permute(0, 2, 3, 1).reshape(-1, 3)     # [P, 3]
+    tiles = full.shape[0] // 256
+    out = torch.full_like(full, math.nan) if base is None else base.permute(0, 2, 3, 1).reshape(-1, 3).clone()
+    for bk in range(G):
+        walk = list(range(bk, tiles, G))
+        for k, t in enumerate(walk):
+            if mutation == "last ragged tile skipped" and t == tiles - 1:
+                continue
+            src = t
+            if mutation == "next halo from tile t + 1" and k > 0:
+                src = min(walk[k - 1] + 1, tiles - 1)        # the halo held in registers belongs to the wrong tile
+            v = full[src * 256:(src + 1) * 256]
+            out[t * 256:(t + 1) * 256] = v if base is None else out[t * 256:(t + 1) * 256] + v
+    return out.reshape(n, h, w, 3).permute(0, 3, 1, 2)
+
+
+@pytest.mark.parametrize("acc", [False, True], ids=["write", "accumulate"])
+def test_ideal_image_grad_walk_inside_bound_and_broken_rejected(acc):
+    """11 tiles over 4 workgroups: workgroups with 3 and with 2 tiles (the
+    ragged walk of 65 x 64 x 64 over 512 workgroups, scaled down)"""
+    g = rnd(11, 64, 16, 16, seed=74).to(BF).float()
+    wt = (rnd(64, 3, 3, 3, seed=75) * 0.1).to(BF).float()
+    base = rnd(11, 3, 16, 16, seed=76) if acc else None
+    rb = parity.conv_in_dgrad_bounds(g, wt, base)
+    parity.assert_within(_emu_image_grad(g, wt, base, 4), *rb, "ideal walk", nchw=True)
+    for m in ("next halo from tile t + 1", "last ragged tile skipped"):
+        got = _emu_image_grad(g, wt, base, 4, mutation=m)
+        with pytest.raises(AssertionError):
+            parity.assert_within(got, *rb, m, nchw=True)
+        score = rel(torch.nan_to_num(nhwc(got)), rb[0])
+        print(f"image grad '{m}' acc {acc}: relative L2 {score:.2e} (unwritten elements counted as 0);"
+              " the older check asserts < 1e-5 over the tensor and per image")
+
+
+def _emu_conv_out_bwd(dy, x, wt, mask, dt, mutation=None):
+    """rr_conv_out_bwd as the ideal kernel: dx = K = cout fp32 products, one
+    store; dw / db one fp32 sum per range of ``conv_out_split`` in a shuffled
+    order, the slabs [(cout + 1)][cin] summed in fp64, one fp32 store"""
+    cout, cin = wt.shape
+    n, _, h, w = dy.shape
+    P = n * h * w
+    blocks, ppb = parity.conv_out_split(P)
+    d2, x2 = dy.permute(0, 2, 3, 1).reshape(P, cout), x.reshape(P, cin)
+    keep = (x2 >= 0) if mutation == "mask x >= 0" else (x2 > 0)
+    gx = d2 @ wt
+    dx = (torch.where(keep, gx, torch.zeros(())) if mask else gx).to(dt).float()
+    ws = torch.zeros(blocks * (cout + 1) * cin + 4096)                    # the slabs, then what lies behind them
+    for bk in range(blocks):
+        pb, pe = bk * ppb, min(P, (bk + 1) * ppb)
+        live = torch.arange(pb, pe)
+        if mutation == "trailing pixels of the pair loop dropped":
+            off = live - pb
+            tail = (off % 64 < 32) & (live + 32 >= pe)
+            dx[live[tail]] = math.nan
+            live = live[~tail]
+        live = live[_shuffle(len(live), 11 + bk)]
+        o = bk * (cout + 1) * cin
+        ws[o:o + cout * cin] = (d2[live].t() @ x2[live]).reshape(-1)
+        ws[o + cout * cin:o + cout * cin + cout] = d2[live].sum(0)
+    slab = ws[:blocks * (cout + 1) * cin].reshape(blocks, cout + 1, cin).double()
+    dw = slab[:, :cout].sum(0).float()
+    if mutation == "db summed with the slab stride of cin rows":
+        idx = torch.arange(blocks)[:, None] * (cin + 1) * cin + cout * cin + torch.arange(cout)[None, :]
+        db = ws[idx.clamp_max(ws.numel() - 1)].double().sum(0).float()
+    else:
+        db = slab[:, cout, :cout].sum(0).float()
+    return dx.reshape(n, h, w, cin), dw, db
+
+
+OUTBWD_MUTATIONS = {
+    "trailing pixels of the pair loop dropped": (64, 3, (1, 3, 11)),      # P = 33: lane 0 takes the pair (0, 32), lanes 1..31 the trailing call
+    "mask x >= 0": (64, 3, (1, 5, 7)),
+    "db summed with the slab stride of cin rows": (12, 3, (2, 33, 31)),   # two ranges: the second slab is misplaced
+}
+
+
+def _outbwd_case(cin, cout, shape, dt):
+    n, h, w = shape
+    dy = rnd(n, cout, h, w, seed=81)
+    x = rnd(n, h, w, cin, seed=82).to(dt).float()
+    x = torch.where(torch.rand(x.shape, generator=torch.Generator().manual_seed(87)) < 0.02, torch.zeros(()), x)
+    return dy, x, rnd(cout, cin, seed=83) / 4.0
+
+
+@pytest.mark.parametrize("dt", [BF, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("cin,cout,shape", [(64, 3, (1, 3, 11)), (64, 3, (2, 33, 31)), (12, 3, (1, 32, 33)), (4, 1, (1, 5, 7))])
+def test_ideal_conv_out_bwd_inside_bounds(cin, cout, shape, dt):
+    dy, x, wt = _outbwd_case(cin, cout, shape, dt)
+    for mask in (0, 1):
+        rb = parity.conv_out_bwd_bounds(dy, x, wt, mask, dt)
+        got = dict(zip(("dx", "dw", "db"), _emu_conv_out_bwd(dy, x, wt, mask, dt)))
+        for key in got:
+            parity.assert_within(got[key], *rb[key], f"ideal {key}")
+        print(f"conv_out_bwd {cin}->{cout} {shape} {dt} mask {mask}: ideal uses "
+              + " ".join(f"{parity.worst_ratio(got[k], *rb[k]):.3f} ({k})" for k in got))
+
+
+@pytest.mark.parametrize("mutation", list(OUTBWD_MUTATIONS))
+def test_broken_conv_out_bwd_rejected(mutation):
+    cin, cout, shape = OUTBWD_MUTATIONS[mutation]
+    dy, x, wt = _outbwd_case(cin, cout, shape, BF)
+    rb = parity.conv_out_bwd_bounds(dy, x, wt, 1, BF)
+    got = dict(zip(("dx", "dw", "db"), _emu_conv_out_bwd(dy, x, wt, 1, BF, mutation=mutation)))
+    bad = []
+    for key in got:
+        try:
+            parity.assert_within(got[key], *rb[key], mutation)
+        except AssertionError:
+            bad.append(key)
+    assert bad, mutation
+    print(f"'{mutation}' {cin}->{cout} {shape}: outside the bound: {bad}; relative L2 "
+          + " ".join(f"{rel(torch.nan_to_num(got[k]), rb[k][0]):.2e} ({k})" for k in got)
+          + "; the older check is close() at 5e-2 on one shape, 2 x 12 x 8")
+
+
+def test_conv_out_db_row_layout():
+    """the finding behind the cin >= cout rule of rr_conv_out_bwd, from the
+    layout alone: the kernel's db index of the last workgroup against the end
+    of the slab area the workspace query sizes"""
+    for cin, cout in ((2, 3), (1, 2), (3, 4), (1, 4)):
+        for blocks in (1, 2, 7):
+            last = ((blocks - 1) * (cout + 1) + cout) * cin + (cout - 1)
+            assert last >= blocks * (cout + 1) * cin and not parity.conv_out_db_row_holds(cin, cout)
+    for cin, cout in ((3, 3), (4, 3), (12, 1), (64, 3), (64, 4)):
+        for blocks in (1, 2, 7):
+            last = ((blocks - 1) * (cout + 1) + cout) * cin + (cout - 1)
+            assert last < blocks * (cout + 1) * cin and parity.conv_out_db_row_holds(cin, cout)
+
+
+@pytest.mark.parametrize("dt", [BF, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("count", [1, 4093, 4096, 8200])
+def test_ideal_prelu_bwd_inside_bounds(count, dt):
+    """the grid-stride split of prelu_bwd_kernel: thread (b, l) takes vectors
+    b 256 + l, + blocks 256, ...; per-thread fp32 chains, a tree per
+    workgroup (torch's fp32 sum here), fp64 across, one store"""
+    blocks = max(1, min(1024, (count + 4095) // 4096))
+    dy, t = rnd(count, seed=91).to(dt).float(), (rnd(count, seed=92) - 0.3).to(dt).float()
+    rb = parity.prelu_bwd_bounds(dy, t, 0.25, dt, blocks)
+    dx = torch.where(t > 0, dy, 0.25 * dy).to(dt)
+    term = torch.where(t > 0, torch.zeros(()), dy * t)
+    n4 = count // 4
+    vec = torch.arange(n4)
+    owner = (vec // 256) % blocks
+    tot = 0.0
+    for b in range(blocks):
+        part = term[:n4 * 4].reshape(n4, 4)[owner == b].reshape(-1)
+        if b == 0:
+            part = torch.cat((part, term[n4 * 4:]))
+        tot += float(part[_shuffle(len(part), b)].sum()) if len(part) else 0.0
+    parity.assert_within(dx, *rb["dx"], "ideal dx")
+    parity.assert_within(torch.tensor(tot).float(), *rb["dalpha"], "ideal dalpha")
+    # broken: the tail dropped (what a count % 4 != 0 call would have lost)
+    if count % 4 and float(term[n4 * 4:].abs().sum()) > 0:
+        with pytest.raises(AssertionError):
+            parity.assert_within(torch.tensor(float(term[:n4 * 4].double().sum())).float(), *rb["dalpha"], "tail dropped")
