@@ -216,6 +216,7 @@ struct RrPath {
   int stream3 = 1, stream3_strips = 1, stream1 = 1, stream1_minp = 131072;
   int conv3r = 1, conv3r_w64 = 1, conv3r_wg = 0, conv3r_segwg = 0;
   int igemm_halo = 1, swgrad = 1, wgrad_halo = 1, blur_tiled = 1;
+  int rdist_tile = 32;                 // ragged distortion tile side: 16, 32 or 64 (else 32)
 };
 
 static inline RrPath rr_path_read() {
@@ -228,7 +229,8 @@ static inline RrPath rr_path_read() {
       {"conv3r", &RrPath::conv3r}, {"conv3r_w64", &RrPath::conv3r_w64},
       {"conv3r_wg", &RrPath::conv3r_wg}, {"conv3r_segwg", &RrPath::conv3r_segwg},
       {"igemm_halo", &RrPath::igemm_halo}, {"swgrad", &RrPath::swgrad},
-      {"wgrad_halo", &RrPath::wgrad_halo}, {"blur_tiled", &RrPath::blur_tiled}};
+      {"wgrad_halo", &RrPath::wgrad_halo}, {"blur_tiled", &RrPath::blur_tiled},
+      {"rdist_tile", &RrPath::rdist_tile}};
   unsigned seen = 0;
   for (const char *p = e; *p;) {
     const char *q = p;

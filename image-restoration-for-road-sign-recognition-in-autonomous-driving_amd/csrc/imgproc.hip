@@ -773,16 +773,17 @@ __global__ void distort_pre_kernel(DistCfg a) {
 }
 
 // stage 2 (blurred images only): filter2D of tmp, then mode 0: the u8 result
-// ((t / 255) * 255 truncated), mode 1: fog + noise on it
-__device__ __forceinline__ void blur_store(const DistCfg &a, const rr_distort_param &p, long long q,
-                                           const float *s) {
+// ((t / 255) * 255 truncated), mode 1: fog + noise on it.  The pixel's a.c
+// bytes go to dst; e0 is its first element's noise index (the dense batch:
+// the same number as its place in out; a ragged batch: elem_base order)
+__device__ __forceinline__ void blur_store(const DistCfg &a, const rr_distort_param &p, long long e0,
+                                           uint8_t *dst, const float *s) {
 #pragma clang fp contract(off)
   for (int c = 0; c < a.c; ++c) {
     float r = rintf(s[c]);                                   // saturate_cast<uchar>: cvRound
     r = r < 0.f ? 0.f : (r > 255.f ? 255.f : r);
-    const long long e = q * a.c + c;
     const float t = (float)(int)r / 255.0f;
-    a.out[e] = a.mode == 0 ? trunc_u8f(t * 255.f) : fog_noise(a, p, t, e);
+    dst[c] = a.mode == 0 ? trunc_u8f(t * 255.f) : fog_noise(a, p, t, e0 + c);
   }
 }
 
@@ -809,7 +810,7 @@ __global__ void distort_blur_kernel(DistCfg a) {
         for (int c = 0; c < a.c; ++c) s[c] = s[c] + kv * (float)px[c];
       }
     }
-    blur_store(a, p, q, s);
+    blur_store(a, p, q * a.c, a.out + q * a.c, s);
   }
 }
 
@@ -885,7 +886,7 @@ __global__ __launch_bounds__(256) void distort_blur_tiled_kernel(DistCfg a) {
         for (int c = 0; c < a.c; ++c) s[c] = s[c] + w * (float)px[c];
       }
     }
-    blur_store(a, p, q, s);
+    blur_store(a, p, q * a.c, a.out + q * a.c, s);
   }
 }
 
@@ -915,59 +916,284 @@ __device__ __forceinline__ double u01(uint32_t hi, uint32_t lo) {       // [0, 1
   return ((((unsigned long long)hi << 21) ^ lo) & ((1ull << 53) - 1)) * 0x1p-53;
 }
 
+// the Philox key of step s, image i's draws under it, and the step's noise
+// seed: one statement for the dense and the ragged generator, so image i of
+// (seed, step) draws the same in both
+__device__ __forceinline__ unsigned long long draw_key(unsigned long long seed, long long s) {
+  return seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(s + 1));
+}
+
+__device__ void distort_draw_one(int i, unsigned long long key, rr_distort_param *prm, int *tap_idx) {
+#pragma clang fp contract(off)
+  uint32_t a[4] = {(uint32_t)i, 0u, 0x5EED0001u, 0u}, b[4] = {(uint32_t)i, 1u, 0x5EED0001u, 0u};
+  philox4(a, key);
+  philox4(b, key);
+  const double r_fog = u01(a[0], a[1]), r_int = u01(a[2], a[3]);
+  const double r_t = u01(b[0], b[1]), r_noise = u01(b[2], b[3]);
+  uint32_t c[4] = {(uint32_t)i, 2u, 0x5EED0001u, 0u}, d[4] = {(uint32_t)i, 3u, 0x5EED0001u, 0u};
+  philox4(c, key);
+  philox4(d, key);
+  const double r_var = u01(c[0], c[1]), r_blur = u01(c[2], c[3]);
+  const double r_deg = u01(d[0], d[1]), r_ang = u01(d[2], d[3]);
+  rr_distort_param p;
+  p.sigma = 0.0;
+  p.fog_mul = 1.0f;
+  p.fog_add = 0.0f;
+  p.flags = 0;
+  p.ksize = 0;
+  int ti = 0;
+  if (r_fog < 0.5) {
+    const double intensity = 0.3 + (0.7 - 0.3) * r_int;
+    const double t = 1.0 - intensity * (0.8 + (1.2 - 0.8) * r_t);
+    p.flags |= RR_DISTORT_FOG;
+    p.fog_mul = (float)t;
+    p.fog_add = (float)(0.9 * (1.0 - t));
+  }
+  if (r_noise < 0.5) {
+    const double var = 0.01 + (0.03 - 0.01) * r_var;
+    p.flags |= RR_DISTORT_NOISE;
+    p.sigma = sqrt(var);
+  }
+  if (r_blur < 0.5) {
+    const int deg = DRAW_DEG0 + (int)(r_deg * DRAW_NDEG);
+    const int ang = (int)(r_ang * DRAW_NANG);
+    p.flags |= RR_DISTORT_BLUR;
+    p.ksize = deg;
+    ti = (deg - DRAW_DEG0) * DRAW_NANG + ang;
+  }
+  *prm = p;
+  *tap_idx = ti;
+}
+
+__device__ __forceinline__ unsigned long long draw_noise_seed(unsigned long long key) {
+  uint32_t e[4] = {0xFFFFFFFFu, 0u, 0x5EED0002u, 0u};
+  philox4(e, key);
+  return ((unsigned long long)e[0] << 32) | e[1];
+}
+
 __global__ __launch_bounds__(256) void distort_draw_kernel(int n, unsigned long long seed,
                                                            long long *step, rr_distort_param *prm,
                                                            int *tap_idx, unsigned long long *noise_seed) {
-#pragma clang fp contract(off)
   const long long s = *step;
-  const unsigned long long key = seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(s + 1));
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    uint32_t a[4] = {(uint32_t)i, 0u, 0x5EED0001u, 0u}, b[4] = {(uint32_t)i, 1u, 0x5EED0001u, 0u};
-    philox4(a, key);
-    philox4(b, key);
-    const double r_fog = u01(a[0], a[1]), r_int = u01(a[2], a[3]);
-    const double r_t = u01(b[0], b[1]), r_noise = u01(b[2], b[3]);
-    uint32_t c[4] = {(uint32_t)i, 2u, 0x5EED0001u, 0u}, d[4] = {(uint32_t)i, 3u, 0x5EED0001u, 0u};
-    philox4(c, key);
-    philox4(d, key);
-    const double r_var = u01(c[0], c[1]), r_blur = u01(c[2], c[3]);
-    const double r_deg = u01(d[0], d[1]), r_ang = u01(d[2], d[3]);
-    rr_distort_param p;
-    p.sigma = 0.0;
-    p.fog_mul = 1.0f;
-    p.fog_add = 0.0f;
-    p.flags = 0;
-    p.ksize = 0;
-    int ti = 0;
-    if (r_fog < 0.5) {
-      const double intensity = 0.3 + (0.7 - 0.3) * r_int;
-      const double t = 1.0 - intensity * (0.8 + (1.2 - 0.8) * r_t);
-      p.flags |= RR_DISTORT_FOG;
-      p.fog_mul = (float)t;
-      p.fog_add = (float)(0.9 * (1.0 - t));
-    }
-    if (r_noise < 0.5) {
-      const double var = 0.01 + (0.03 - 0.01) * r_var;
-      p.flags |= RR_DISTORT_NOISE;
-      p.sigma = sqrt(var);
-    }
-    if (r_blur < 0.5) {
-      const int deg = DRAW_DEG0 + (int)(r_deg * DRAW_NDEG);
-      const int ang = (int)(r_ang * DRAW_NANG);
-      p.flags |= RR_DISTORT_BLUR;
-      p.ksize = deg;
-      ti = (deg - DRAW_DEG0) * DRAW_NANG + ang;
-    }
-    prm[i] = p;
-    tap_idx[i] = ti;
-  }
+  const unsigned long long key = draw_key(seed, s);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) distort_draw_one(i, key, prm + i, tap_idx + i);
   __syncthreads();
   if (threadIdx.x == 0) {
-    uint32_t e[4] = {0xFFFFFFFFu, 0u, 0x5EED0002u, 0u};
-    philox4(e, key);
-    *noise_seed = ((unsigned long long)e[0] << 32) | e[1];
+    *noise_seed = draw_noise_seed(key);
     *step = s + 1;
   }
+}
+
+// ------------------------------------------------- ragged distortion ----
+// The same generator for n images of unequal size in one byte buffer, each at
+// its NATIVE size, as the reference distorts them before it resizes anything
+// (14:75-93; 16:44-58 for the compound form): two launches whatever n is, no
+// per-image host work, the table and the step counter read on the device only.
+//   1. rdist_prologue_kernel (one workgroup): elem_base[i], the exclusive
+//      prefix sum of h * w * c over the records in table order (an invalid
+//      record counts 0): the element index that keys the Philox noise and
+//      indexes the explicit noise field.  Images back to back in table order
+//      thus use the dense op's element indices, whatever the byte offsets
+//      are.  The random variant makes the per-image draws here too.
+//   2. rdist_tile_kernel: one workgroup per (image, TH x TW tile of output
+//      pixels).  For a blurred image it computes the blur INPUT of its tile
+//      plus the k - 1 halo straight into LDS -- the source coordinate
+//      reflected (101), the noise taken at the reflected source element's
+//      index, so a halo byte is the byte the two-pass form reads back from its
+//      staging image -- compacts the nonzero taps (row-major), and after one
+//      barrier runs the fp32 tap sum out of LDS.  The staging image never
+//      reaches HBM; the price is that a halo element's fog / noise is
+//      computed by every tile that reads it.
+// A record that fails rd_valid (rg_valid, or a blur flag with ksize outside
+// [1, KMAX]) reads nothing and writes nothing.
+struct RdArgs {
+  DistCfg d;                            // n, mode, in, out, prm, taps, noise, seeds; h, w = max_h, max_w
+  const rr_ragged_image *tab;
+  long long in_bytes;
+  long long *elem_base;                 // [n], workspace
+  int tiles_y, tiles_x;                 // tiles of a max_h x max_w image
+};
+
+__device__ __forceinline__ bool rd_valid(const rr_ragged_image &r, const rr_distort_param &p, int c,
+                                         int max_h, int max_w, long long in_bytes) {
+  if ((p.flags & RR_DISTORT_BLUR) && (p.ksize < 1 || p.ksize > RR_DISTORT_KMAX)) return false;
+  return rg_valid(r, c, max_h, max_w, in_bytes);
+}
+
+// draw != 0: image i's draws of (seed, *step) into prm_out / idx_out (= a.d.prm
+// / a.d.tap_idx), the step's noise seed, *step += 1 -- distort_draw_kernel's
+// work, by the same device functions
+__global__ __launch_bounds__(256) void rdist_prologue_kernel(RdArgs a, int draw, unsigned long long seed,
+                                                             long long *step, rr_distort_param *prm_out,
+                                                             int *idx_out, unsigned long long *noise_seed) {
+  __shared__ long long scan[256];
+  const int t = threadIdx.x;
+  long long s = 0;
+  unsigned long long key = 0;
+  if (draw) {
+    s = *step;
+    key = draw_key(seed, s);
+  }
+  long long carry = 0;                                      // elements of the records before this chunk
+  for (int i0 = 0; i0 < a.d.n; i0 += 256) {
+    const int i = i0 + t;
+    long long v = 0;
+    if (i < a.d.n) {
+      rr_distort_param p;
+      if (draw) {
+        int ti;
+        distort_draw_one(i, key, &p, &ti);
+        prm_out[i] = p;
+        idx_out[i] = ti;
+      } else {
+        p = a.d.prm[i];
+      }
+      const rr_ragged_image r = a.tab[i];
+      if (rd_valid(r, p, a.d.c, a.d.h, a.d.w, a.in_bytes)) v = (long long)r.h * r.w * a.d.c;
+    }
+    scan[t] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {                     // inclusive scan of the chunk
+      const long long u = t >= o ? scan[t - o] : 0;
+      __syncthreads();
+      scan[t] += u;
+      __syncthreads();
+    }
+    if (i < a.d.n) a.elem_base[i] = carry + scan[t] - v;
+    carry += scan[255];
+    __syncthreads();                                        // scan is rewritten by the next chunk
+  }
+  if (draw && t == 0) {
+    *noise_seed = draw_noise_seed(key);
+    *step = s + 1;
+  }
+}
+
+template <int C, int TH, int TW>
+__global__ __launch_bounds__(256) void rdist_tile_kernel(RdArgs a) {
+#pragma clang fp contract(off)
+  constexpr int K2 = RR_DISTORT_KMAX * RR_DISTORT_KMAX;
+  // a staged pixel takes PS bytes, 4 for 3 channels: the tap loop then reads a
+  // pixel in one aligned LDS load (3-byte pixels made it a misaligned 16-bit
+  // load plus a byte load per tap, and the tap loop the slowest part of the
+  // call by far)
+  constexpr int PS = C == 3 ? 4 : C;
+  using Pix = std::conditional_t<PS == 4, uint32_t, std::conditional_t<PS == 2, uint16_t, uint8_t>>;
+  __shared__ Pix simg[(TH + RR_DISTORT_KMAX - 1) * (TW + RR_DISTORT_KMAX - 1)];
+  __shared__ float tv[K2];
+  __shared__ int ti[K2];
+  __shared__ int ntaps;
+  const int t = threadIdx.x;
+  const int tiles = a.tiles_y * a.tiles_x;
+  const int img = blockIdx.x / tiles, tl = blockIdx.x - img * tiles;
+  const int y0 = (tl / a.tiles_x) * TH, x0 = (tl % a.tiles_x) * TW;
+  const rr_ragged_image r = a.tab[img];
+  const rr_distort_param p = a.d.prm[img];
+  // uniform over the workgroup, and before any barrier
+  if (!rd_valid(r, p, C, a.d.h, a.d.w, a.in_bytes) || y0 >= r.h || x0 >= r.w) return;
+  const int th = r.h - y0 < TH ? r.h - y0 : TH, tw = r.w - x0 < TW ? r.w - x0 : TW;
+  DistCfg d = a.d;
+  d.c = C;
+  const long long eb = a.elem_base[img];
+  const uint8_t *src = d.in + r.offset;
+  uint8_t *dst = d.out + r.offset;
+  if (!(p.flags & RR_DISTORT_BLUR)) {                        // distort_pre_kernel's expression
+    const int rowb = tw * C;
+    for (int i = t; i < th * rowb; i += 256) {
+      const int ly = i / rowb;
+      const long long le = ((long long)(y0 + ly) * r.w + x0) * C + (i - ly * rowb);
+      const float x = (float)src[le] / 255.0f;
+      if (d.mode == 0) dst[le] = fog_noise(d, p, x, eb + le);
+      else dst[le] = fog_noise(d, p, (float)trunc_u8f(x * 255.f) / 255.0f, eb + le);
+    }
+    return;
+  }
+  const int k = p.ksize, anc = k / 2;
+  // the nonzero taps in row-major order (cv2 drops zero taps), listed by the
+  // first wave alone: tap u = lane + 64 j, so the ballots come in tap order
+  if (t < 64) {
+    const float *kt = d.taps + (long long)(d.tap_idx ? d.tap_idx[img] : img) * K2;
+    int off = 0;
+#pragma unroll
+    for (int j = 0; j < (K2 + 63) / 64; ++j) {
+      const int u = t + 64 * j, ki = u / k, kj = u - ki * k;
+      const float kv = u < k * k ? kt[ki * RR_DISTORT_KMAX + kj] : 0.f;
+      const bool nz = kv != 0.f;
+      const unsigned long long m = __ballot(nz);
+      if (nz) {
+        const int pos = off + __popcll(m & ((1ull << t) - 1ull));
+        tv[pos] = kv;
+        ti[pos] = (ki << 8) | kj;
+      }
+      off += __popcll(m);
+    }
+    if (t == 0) ntaps = off;
+  }
+  // the blur input of the tile and its halo: rows y0 - anc .. y0 + th + k - 2 -
+  // anc, columns likewise, each at its reflected source element
+  const int pw = tw + k - 1, nr = th + k - 1, rowb = pw * C;
+  for (int e = t; e < nr * rowb; e += 256) {
+    const int ry = e / rowb, rest = e - ry * rowb;
+    const int cx = rest / C, ch = rest - cx * C;
+    const int yy = reflect101(y0 - anc + ry, r.h), xx = reflect101(x0 - anc + cx, r.w);
+    const long long le = ((long long)yy * r.w + xx) * C + ch;
+    const float x = (float)src[le] / 255.0f;
+    ((uint8_t *)simg)[(ry * pw + cx) * PS + ch] = d.mode == 0 ? fog_noise(d, p, x, eb + le) : trunc_u8f(x * 255.f);
+  }
+  __syncthreads();
+  const int nt = ntaps;
+  for (int i = t; i < th * tw; i += 256) {
+    const int ly = i / tw, lx = i - ly * tw;
+    const Pix *base = simg + ly * pw + lx;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < nt; ++u) {
+      const int ij = ti[u];
+      const float w = tv[u];
+      const uint32_t px = base[(ij >> 8) * pw + (ij & 255)];
+#pragma unroll
+      for (int c = 0; c < C; ++c) s[c] = s[c] + w * (float)((px >> (8 * c)) & 255u);
+    }
+    const long long le = ((long long)(y0 + ly) * r.w + (x0 + lx)) * C;
+    blur_store(d, p, eb + le, dst + le, s);
+  }
+}
+
+// workspace of both ragged entry points: elem_base[n], then the random
+// variant's draws in rr_distort_random_u8's order (params, table indices, noise
+// seed).  No image-sized term: nothing is staged in HBM.
+struct RdPlan {
+  size_t off_prm, off_idx, off_seed, total;
+};
+
+static int rd_plan(int n, int c, int max_h, int max_w, RdPlan *p) {
+  if (n <= 0 || c < 1 || c > 4 || max_h < 1 || max_w < 1) return RR_EINVAL;
+  auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  p->off_prm = al((size_t)n * sizeof(long long));
+  p->off_idx = al(p->off_prm + (size_t)n * sizeof(rr_distort_param));
+  p->off_seed = al(p->off_idx + (size_t)n * sizeof(int));
+  p->total = p->off_seed + 16;
+  return RR_OK;
+}
+
+// the tile shape: 32 x 32 unless RR_PATH rdist_tile names one of the other
+// two measured shapes (tools/bench_ragged_distort.py)
+static int rd_launch(RdArgs a, int c, int max_h, int max_w, int tile, hipStream_t st) {
+  auto go = [&](auto th, auto tw) {
+    constexpr int TH = decltype(th)::value, TW = decltype(tw)::value;
+    a.tiles_y = (max_h + TH - 1) / TH;
+    a.tiles_x = (max_w + TW - 1) / TW;
+    const long long groups = (long long)a.d.n * a.tiles_y * a.tiles_x;
+    if (groups >= (1LL << 31)) return (int)RR_EUNSUPPORTED;
+    return rr_dispatch_int<1, 2, 3, 4>(c, [&](auto cc) {
+      hipLaunchKernelGGL((rdist_tile_kernel<decltype(cc)::value, TH, TW>), dim3((unsigned)groups), dim3(256), 0,
+                         st, a);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
+  };
+  if (tile == 16) return go(ic<16>{}, ic<16>{});
+  if (tile == 64) return go(ic<64>{}, ic<64>{});
+  return go(ic<32>{}, ic<32>{});
 }
 
 extern "C" size_t rr_distort_workspace(int n, int h, int w, int c) {
@@ -1092,5 +1318,63 @@ extern "C" int rr_distort_random_draws(int n, int h, int w, int c, const void *w
   *prm_off = draw_off_prm(n, h, w, c);
   *idx_off = *prm_off + (size_t)n * sizeof(rr_distort_param);
   *seed_off = *idx_off + ((size_t)n * 4 + 15) / 16 * 16;
+  return RR_OK;
+}
+
+// ------------------------------------------- ragged distortion: C ABI ----
+extern "C" size_t rr_distort_ragged_workspace(int n, int c, int max_h, int max_w) {
+  RdPlan p;
+  return rd_plan(n, c, max_h, max_w, &p) == RR_OK ? p.total : 0;
+}
+
+extern "C" int rr_distort_ragged_u8(int n, int c, int mode, int max_h, int max_w, const uint8_t *in,
+                                    size_t in_bytes, const rr_ragged_image *images_dev, uint8_t *out,
+                                    const rr_distort_param *params, const float *taps, const int *tap_idx,
+                                    const double *noise, unsigned long long seed, void *ws, size_t ws_bytes,
+                                    rr_stream stream) {
+  RdPlan p;
+  if (!in || !images_dev || !out || !params || !taps || !ws || in == out) return RR_EINVAL;   // halo reads: not in place
+  if (in_bytes == 0 || in_bytes > (size_t)INT64_MAX || (mode != 0 && mode != 1)) return RR_EINVAL;
+  if (const int rc = rd_plan(n, c, max_h, max_w, &p)) return rc;
+  if (ws_bytes < p.total) return RR_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  RdArgs a{DistCfg{n, max_h, max_w, c, mode, in, out, nullptr, params, taps, noise, seed, tap_idx, nullptr},
+           images_dev, (long long)in_bytes, (long long *)ws, 0, 0};
+  hipLaunchKernelGGL(rdist_prologue_kernel, dim3(1), dim3(256), 0, st, a, 0, 0ull, (long long *)nullptr,
+                     (rr_distort_param *)nullptr, (int *)nullptr, (unsigned long long *)nullptr);
+  RR_CHECK_LAUNCH();
+  return rd_launch(a, c, max_h, max_w, rr_path_read().rdist_tile, st);
+}
+
+extern "C" int rr_distort_random_ragged_u8(int n, int c, int max_h, int max_w, const uint8_t *in,
+                                           size_t in_bytes, const rr_ragged_image *images_dev, uint8_t *out,
+                                           unsigned long long seed, long long *step, const float *table,
+                                           void *ws, size_t ws_bytes, rr_stream stream) {
+  RdPlan p;
+  if (!in || !images_dev || !out || !step || !table || !ws || in == out) return RR_EINVAL;
+  if (in_bytes == 0 || in_bytes > (size_t)INT64_MAX) return RR_EINVAL;
+  if (const int rc = rd_plan(n, c, max_h, max_w, &p)) return rc;
+  if (ws_bytes < p.total) return RR_EWORKSPACE;
+  char *base = (char *)ws;
+  rr_distort_param *prm = (rr_distort_param *)(base + p.off_prm);
+  int *tap_idx = (int *)(base + p.off_idx);
+  unsigned long long *nseed = (unsigned long long *)(base + p.off_seed);
+  hipStream_t st = (hipStream_t)stream;
+  RdArgs a{DistCfg{n, max_h, max_w, c, 0, in, out, nullptr, prm, table, nullptr, 0ull, tap_idx, nseed},
+           images_dev, (long long)in_bytes, (long long *)ws, 0, 0};
+  hipLaunchKernelGGL(rdist_prologue_kernel, dim3(1), dim3(256), 0, st, a, 1, seed, step, prm, tap_idx, nseed);
+  RR_CHECK_LAUNCH();
+  return rd_launch(a, c, max_h, max_w, rr_path_read().rdist_tile, st);
+}
+
+// the draws of the last rr_distort_random_ragged_u8 call, as rr_distort_random_draws
+extern "C" int rr_distort_random_ragged_draws(int n, int c, int max_h, int max_w, const void *ws,
+                                              size_t *prm_off, size_t *idx_off, size_t *seed_off) {
+  RdPlan p;
+  if (!ws || !prm_off || !idx_off || !seed_off) return RR_EINVAL;
+  if (const int rc = rd_plan(n, c, max_h, max_w, &p)) return rc;
+  *prm_off = p.off_prm;
+  *idx_off = p.off_idx;
+  *seed_off = p.off_seed;
   return RR_OK;
 }

@@ -232,6 +232,13 @@ _SIGS = {
     "rr_distort_random_u8": (I_, [I_, I_, I_, I_, P_, P_, C.c_ulonglong, P_, P_, P_, S_, P_]),
     "rr_distort_random_draws": (I_, [I_, I_, I_, I_, P_, C.POINTER(S_), C.POINTER(S_),
                                      C.POINTER(S_)]),
+    "rr_distort_ragged_workspace": (S_, [I_, I_, I_, I_]),
+    "rr_distort_ragged_u8": (I_, [I_, I_, I_, I_, I_, P_, S_, P_, P_, P_, P_, P_, P_, C.c_ulonglong,
+                                  P_, S_, P_]),
+    "rr_distort_random_ragged_u8": (I_, [I_, I_, I_, I_, P_, S_, P_, P_, C.c_ulonglong, P_, P_, P_, S_,
+                                         P_]),
+    "rr_distort_random_ragged_draws": (I_, [I_, I_, I_, I_, P_, C.POINTER(S_), C.POINTER(S_),
+                                            C.POINTER(S_)]),
     "rr_linear_wgrad": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, I_, P_]),
     "rr_linear_dgrad": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, P_]),
     "rr_dropout_fwd": (I_, [L_, F_, C.c_ulonglong, P_, P_, P_, P_, P_]),

@@ -26,6 +26,11 @@ DataLoader workers and in the inference loop).  Here they take a whole
   07:52-66 and the mixed ``.ppm`` + ``.png`` list of 08:84-88 into the same
   ``RaggedBatch``: inflate on host threads, the row filters undone and
   ``convert('RGB')`` applied on the device for the whole batch in one launch.
+* ``DynamicDistortionDataset`` -- 14:66-93: files -> ``(bad, clean)`` tensor
+  pairs, the distortion applied to every image at its NATIVE size before the
+  resize, as the reference does; ``apply_random_distortions``,
+  ``apply_compound_distortion`` and ``RandomDistortion`` take a ``RaggedBatch``
+  for that (two launches per batch, the blur input kept on chip).
 """
 from __future__ import annotations
 
@@ -44,7 +49,7 @@ from ._lib import (PNG_REASON, RR_DISTORT_BLUR, RR_DISTORT_FOG, RR_DISTORT_KMAX,
 
 __all__ = ["Resize", "ToTensor", "Normalize", "Compose", "apply_random_distortions",
            "encode_png", "write_png",
-           "RandomDistortion", "motion_blur_table",
+           "RandomDistortion", "motion_blur_table", "DynamicDistortionDataset",
            "apply_compound_distortion", "distortion_params", "psnr", "ssim", "cv_resize",
            "RaggedBatch", "read_ppm", "read_png", "read_images", "ImageFolder", "find_images",
            "IMAGENET_MEAN", "IMAGENET_STD"]
@@ -229,6 +234,22 @@ class RaggedBatch:
         for a, o, nb in zip(arrs, rec["offset"], nbytes):
             buf[o:o + nb] = a.reshape(-1)
         return cls(host[:max(int(nbytes.sum()), 1)].to(device, non_blocking=True), rec, c)
+
+    def with_data(self, data):
+        """another buffer under this batch's records: the batch an op returns
+        that writes every image at its own offset (the ragged distortions).
+        It SHARES ``table``, ``records`` and ``max_hw`` -- no check, no copy,
+        nothing a graph capture could not hold -- so a table overwritten in
+        place is seen through both."""
+        if (not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1
+                or data.numel() != self.data.numel() or data.device != self.data.device
+                or not data.is_contiguous()):
+            raise TypeError("RaggedBatch.with_data: expected a contiguous 1-D uint8 buffer of the same "
+                            "size on the same device")
+        b = object.__new__(RaggedBatch)
+        b.data, b.records, b.channels, b.max_hw = data, self.records, self.channels, self.max_hw
+        b.sizes, b.table = self.sizes, self.table
+        return b
 
     def resize(self, oh, ow, out="u8", mean=None, std=None):
         """every image through PIL's bilinear resample to (oh, ow): the dense
@@ -539,12 +560,29 @@ def distortion_params(n, rng=None):
     return params, taps
 
 
+def _distort_ragged(x, params, taps, mode, noise, seed):
+    """ops.distort_ragged_u8 on a RaggedBatch -> the RaggedBatch of the results
+    under the same records (``noise``: 1-D fp64, packed in table order)"""
+    ops._need_cuda(x.data)
+    if noise is not None:
+        noise = noise.reshape(-1)
+    y = ops.distort_ragged_u8(x.data, x.table, x.max_hw, x.channels, params, taps, mode=mode,
+                              noise=noise, seed=seed)
+    return x.with_data(y)
+
+
 def apply_random_distortions(x, rng=None, seed=None, noise=None):
-    """14:31-64 on a [n, h, w, c] uint8 device batch."""
-    _check_u8(x)
-    params, taps = distortion_params(x.shape[0], rng)
+    """14:31-64 on a [n, h, w, c] uint8 device batch, or on a RaggedBatch:
+    every image at its native size, as 14:75-93 calls it before the resize
+    (-> a RaggedBatch under the same records)."""
+    ragged = isinstance(x, RaggedBatch)
+    if not ragged:
+        _check_u8(x)
+    params, taps = distortion_params(len(x) if ragged else x.shape[0], rng)
     if seed is None:
         seed = (rng or _random).getrandbits(64)
+    if ragged:
+        return _distort_ragged(x, params, taps, 0, noise, seed)
     return ops.distort_u8(x, params, taps, mode=0, noise=noise, seed=seed)
 
 
@@ -573,7 +611,9 @@ class RandomDistortion:
     (rr_distort_random_u8): graph-capturable, so a captured training step
     re-draws on every replay.  The draws follow the reference's distributions
     (Philox4x32-10 keyed by (seed, step); the reference's stream is unseeded);
-    the step counter lives in device memory and advances once per call.
+    the step counter lives in device memory and advances once per call.  A
+    ``RaggedBatch`` in place of the tensor is distorted image by image at
+    native size and comes back as a ``RaggedBatch`` under the same records.
 
     ``last_draws()`` reads the most recent draws back (tests)."""
 
@@ -586,6 +626,8 @@ class RandomDistortion:
         self._shape = None
 
     def __call__(self, x, out=None):
+        if isinstance(x, RaggedBatch):
+            return self._ragged(x, out)
         _check_u8(x)
         ops._need_cuda(x)
         n, h, w, c = x.shape
@@ -602,14 +644,42 @@ class RandomDistortion:
                 "rr_distort_random_u8")
         return out
 
+    def _ragged(self, x, out):
+        """a RaggedBatch: every image at its native size, as 14:75-93 distorts
+        the file's pixels before the resize (rr_distort_random_ragged_u8) ->
+        the RaggedBatch of the results under the same records.  Image i draws
+        what image i of a dense batch draws at the same (seed, step)."""
+        ops._need_cuda(x.data, x.table)
+        n, c, (max_h, max_w) = len(x), x.channels, x.max_hw
+        L = ops.lib()
+        shape = ("ragged", n, c, max_h, max_w)
+        if self._ws is None or self._shape != shape:
+            self._ws = ops._ws(L.rr_distort_ragged_workspace(n, c, max_h, max_w), self.device)
+            self._shape = shape
+        if out is None:
+            out = torch.empty_like(x.data)
+        y = x.with_data(out)                            # checks out against the batch's buffer
+        L.check(L.rr_distort_random_ragged_u8(n, c, max_h, max_w, x.data.data_ptr(), x.data.numel(),
+                                              x.table.data_ptr(), out.data_ptr(), self.seed,
+                                              self.step.data_ptr(), self.table.data_ptr(),
+                                              self._ws.data_ptr(), self._ws.numel(), ops.stream()),
+                "rr_distort_random_ragged_u8")
+        return y
+
     def last_draws(self):
         """-> (params: list of DistortParam, table index [n] int32, noise seed)"""
         import ctypes as C
-        n, h, w, c = self._shape
         po, io, so = C.c_size_t(), C.c_size_t(), C.c_size_t()
         L = ops.lib()
-        L.check(L.rr_distort_random_draws(n, h, w, c, self._ws.data_ptr(), C.byref(po), C.byref(io),
-                                          C.byref(so)), "rr_distort_random_draws")
+        if self._shape[0] == "ragged":
+            _, n, c, max_h, max_w = self._shape
+            L.check(L.rr_distort_random_ragged_draws(n, c, max_h, max_w, self._ws.data_ptr(), C.byref(po),
+                                                     C.byref(io), C.byref(so)),
+                    "rr_distort_random_ragged_draws")
+        else:
+            n, h, w, c = self._shape
+            L.check(L.rr_distort_random_draws(n, h, w, c, self._ws.data_ptr(), C.byref(po), C.byref(io),
+                                              C.byref(so)), "rr_distort_random_draws")
         raw = self._ws.cpu()
         sz = C.sizeof(DistortParam)
         arr = (DistortParam * n).from_buffer_copy(bytes(raw[po.value:po.value + n * sz].numpy()))
@@ -620,13 +690,68 @@ class RandomDistortion:
 
 def apply_compound_distortion(x, seed=0, noise=None):
     """16:14-37 on a [n, h, w, c] uint8 device batch: blur (10, 45 deg) ->
-    fog (intensity 0.5, A 0.9) -> noise (var 0.02)."""
-    _check_u8(x)
-    n = x.shape[0]
+    fog (intensity 0.5, A 0.9) -> noise (var 0.02); or on a RaggedBatch, every
+    image at its native size as the offline generator reads it (16:44-58) ->
+    a RaggedBatch under the same records."""
+    ragged = isinstance(x, RaggedBatch)
+    if not ragged:
+        _check_u8(x)
+    n = len(x) if ragged else x.shape[0]
     t, A = 1.0 - 0.5, 0.9
     p = DistortParam(0.02 ** 0.5, t, A * (1 - t), RR_DISTORT_FOG | RR_DISTORT_NOISE | RR_DISTORT_BLUR, 10)
     taps = ops.motion_blur_kernel(10, 45).unsqueeze(0).expand(n, -1, -1).contiguous()
+    if ragged:
+        return _distort_ragged(x, [p] * n, taps, 1, noise, seed)
     return ops.distort_u8(x, [p] * n, taps, mode=1, noise=noise, seed=seed)
+
+
+class DynamicDistortionDataset:
+    """The reference's training dataset (14:66-93) in device batches: the file
+    list is ``sorted(clean_root.glob('*/*.ppm'))`` (14:68) and ``len()`` its
+    length (14:72-73).  ``load(indices)`` reads those files with ONE
+    ``read_ppm`` into a RaggedBatch (the clean images), distorts that batch at
+    native size with an owned ``RandomDistortion(device, seed)`` (14:83: the
+    draws on device, one step per batch), and puts both through ``transform``
+    (14:86-91) -> ``(bad, clean)``, 14:93's order.  With 14:202-205's
+    ``Compose([Resize((224, 224)), ToTensor()])`` these are two [n, 3, 224, 224]
+    fp32 tensors; without a transform, two RaggedBatch.  ``batches(batch_size,
+    shuffle, generator)`` yields that for one pass over the files, the last
+    batch short.  The constructor lists files only and touches no device;
+    ``device`` defaults to the GPU when there is one.  ``last_draws()``: the
+    draws of the most recent batch."""
+
+    def __init__(self, clean_root, transform=None, device=None, seed=0, threads=0):
+        self.clean_files = sorted(Path(clean_root).glob('*/*.ppm'))
+        self.transform = transform
+        self.device = device
+        self.seed = seed
+        self.threads = threads
+        self._distort = None
+
+    def __len__(self):
+        return len(self.clean_files)
+
+    def _device(self):
+        return torch.device(self.device if self.device is not None
+                            else ("cuda" if torch.cuda.is_available() else "cpu"))
+
+    def load(self, indices):
+        if self._distort is None:
+            self._distort = RandomDistortion(self._device(), self.seed)
+        clean = read_ppm([self.clean_files[int(i)] for i in indices], self._distort.device, self.threads)
+        bad = self._distort(clean)
+        if self.transform is not None:
+            bad, clean = self.transform(bad), self.transform(clean)
+        return bad, clean
+
+    def batches(self, batch_size, shuffle=False, generator=None):
+        n = len(self.clean_files)
+        order = torch.randperm(n, generator=generator).tolist() if shuffle else list(range(n))
+        for a in range(0, n, int(batch_size)):
+            yield self.load(order[a:a + int(batch_size)])
+
+    def last_draws(self):
+        return self._distort.last_draws()
 
 
 def cv_resize(x, size):

@@ -25,7 +25,7 @@ __all__ = [
     "motion_blur_kernel", "first_conv_wgrad_act", "affine_act_pool", "nearest_resize",
     "nearest_resize_bwd", "fold_conv_bn", "bn_stats", "linear_wgrad", "linear_dgrad",
     "dropout_fwd", "dropout_bwd", "dropout_mask", "cross_entropy", "softmax_max", "sgd_",
-    "resize_ragged_u8", "png_unfilter",
+    "resize_ragged_u8", "png_unfilter", "distort_ragged_u8",
 ]
 
 
@@ -1254,6 +1254,77 @@ def distort_u8(x, params, taps, mode=0, noise=None, seed=0):
     L.check(L.rr_distort_u8(n, h, w, c, int(mode), _p(x), _p(y), _p(prm), _p(taps), _p(noise),
                             int(seed) & (2 ** 64 - 1), _p(ws), wsb, stream()), "rr_distort_u8")
     return y
+
+
+def _ragged_elems(table, params, max_hw, c, in_bytes):
+    """host: the elements rr_distort_ragged_u8 counts (sum of h * w * c over
+    the records it holds valid) -- the length its noise field must have"""
+    t = table.cpu()
+    off, hw = t.view(torch.int64)[:, 0].tolist(), t.view(torch.int32)[:, 2:4].tolist()
+    total = 0
+    for o, (h, w), p in zip(off, hw, params):
+        if (p.flags & 4) and not 1 <= p.ksize <= RR_DISTORT_KMAX:
+            continue
+        if 1 <= h <= max_hw[0] and 1 <= w <= max_hw[1] and 0 <= o and o + h * w * c <= in_bytes:
+            total += h * w * c
+    return total
+
+
+def distort_ragged_u8(data, table, max_hw, c, params, taps, mode=0, noise=None, seed=0, tap_idx=None,
+                      out=None):
+    """distortion generator on n images of unequal size, each at its native
+    size (the reference distorts before it resizes, 14:75-93 / 16:44-58), in
+    two launches.  ``data`` / ``table`` / ``max_hw`` / ``c``: as
+    resize_ragged_u8; ``params``: a list of n DistortParam; ``taps``: [n, KMAX,
+    KMAX] fp32 (host or device), or any [m, KMAX, KMAX] table when ``tap_idx``
+    (device int32 [n]) picks image i's entry; ``noise``: an optional 1-D fp64
+    field, already scaled, in packed element order (image after image in table
+    order, whatever the byte offsets are), else Philox(seed) keyed by that same
+    index.  -> the output buffer, as long as ``data``, image i at its own
+    offset (``out``, when given, is that buffer; no byte outside the images is
+    written).  A record that fails rr_ragged_check, or has the blur flag with
+    ksize outside [1, KMAX], is skipped: nothing read, nothing written."""
+    _need_cuda(data, table, tap_idx, out)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise TypeError("distort_ragged_u8 expects a contiguous 1-D uint8 buffer")
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous():
+        raise TypeError("distort_ragged_u8 expects an [n, 16] uint8 table of rr_ragged_image records")
+    n, c = int(table.shape[0]), int(c)
+    max_h, max_w = int(max_hw[0]), int(max_hw[1])
+    if len(params) != n:
+        raise ValueError("one DistortParam per image")
+    if mode not in (0, 1):
+        raise ValueError(mode)
+    arr = (DistortParam * n)(*params)
+    prm = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(data.device)
+    taps = taps.to(data.device, torch.float32).contiguous()
+    if taps.dim() != 3 or tuple(taps.shape[1:]) != (RR_DISTORT_KMAX, RR_DISTORT_KMAX):
+        raise ValueError("taps must be [n, KMAX, KMAX]")
+    if tap_idx is None:
+        if taps.shape[0] != n:
+            raise ValueError("taps must be [n, KMAX, KMAX]")
+    elif tap_idx.dtype != torch.int32 or tuple(tap_idx.shape) != (n,) or not tap_idx.is_contiguous():
+        raise TypeError("tap_idx must be a contiguous int32 [n] device tensor")
+    if noise is not None:
+        noise = noise.to(data.device, torch.float64).contiguous()
+        need = _ragged_elems(table, params, (max_h, max_w), c, data.numel())
+        if noise.dim() != 1 or noise.numel() < need:
+            raise ValueError(f"noise must be a 1-D field of the batch's {need} elements in table order")
+    if out is None:
+        out = torch.empty_like(data)
+    elif (out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
+          or out.numel() != data.numel() or out.data_ptr() == data.data_ptr()):
+        raise TypeError(f"distort_ragged_u8 out: expected another contiguous 1-D uint8 buffer of "
+                        f"{data.numel()} bytes (the blur reads its neighbours: not in place)")
+    L = lib()
+    wsb = L.rr_distort_ragged_workspace(n, c, max_h, max_w)
+    if wsb == 0:
+        raise RuntimeError(f"rr_distort_ragged_u8: unsupported batch n={n} c={c} max={max_h, max_w}")
+    ws = _ws(wsb, data.device)
+    L.check(L.rr_distort_ragged_u8(n, c, int(mode), max_h, max_w, _p(data), data.numel(), _p(table), _p(out),
+                                   _p(prm), _p(taps), _p(tap_idx), _p(noise), int(seed) & (2 ** 64 - 1),
+                                   _p(ws), wsb, stream()), "rr_distort_ragged_u8")
+    return out
 
 
 def zero_(t):

@@ -826,6 +826,57 @@ int rr_distort_random_u8(int n, int h, int w, int c, const uint8_t *in, uint8_t 
 int rr_distort_random_draws(int n, int h, int w, int c, const void *workspace,
                             size_t *params_off, size_t *index_off, size_t *seed_off);
 
+/* The same generators for a ragged batch (rr_ragged_image table, as
+ * rr_resize_ragged_u8 takes it): the reference distorts every GTSRB image at
+ * its NATIVE size and resizes afterwards (14_train_unified_advanced.py 14:75-93
+ * calls 14:31-64 on the file's pixels; 16:44-58 does the same with the
+ * compound form 16:14-37), and a 5..15-pixel blur of a 30-pixel sign is not
+ * the blur of its 224-pixel enlargement.  Every valid record gets
+ * rr_distort_u8's arithmetic byte for byte; the result is a ragged batch with
+ * the SAME table: `out` is as long as `in` (in_bytes) and image i lands at its
+ * own offset; no other byte of `out` is written.  Two launches whatever n is,
+ * no per-image host work, no float atomics, graph-capturable: table, params
+ * and step counter are read on the device only.
+ *
+ * Element index: the noise (the Philox key, or the index into `noise`) of
+ * element (y, x, ch) of image i is elem_base[i] + (y * w + x) * c + ch, with
+ * elem_base the exclusive prefix sum of h * w * c over the valid records in
+ * table order -- not the byte offset.  Images that lie back to back in table
+ * order therefore use rr_distort_u8's element indices, whatever headers or
+ * gaps the buffer holds; `noise` (already scaled by sigma) holds the sum of
+ * h * w * c doubles in that order.
+ *
+ * Invalid records -- outside [1, max_h] x [1, max_w], leaving [0, in_bytes)
+ * (rr_ragged_check), or RR_DISTORT_BLUR with ksize outside [1, KMAX] -- read
+ * nothing, write nothing and count 0 elements.  The blur input (14:53) is
+ * computed tile by tile on chip, halo included, and never reaches memory: the
+ * workspace holds n prefix sums and the draws, nothing image-sized (the query
+ * ignores max_h / max_w beyond their sign).  taps: [n][KMAX][KMAX], or any
+ * table indexed by tap_idx[n] when that is given.
+ * RR_EINVAL: a null required pointer, n <= 0, c outside 1..4, mode outside
+ * {0, 1}, max_h / max_w < 1, in_bytes == 0, or in == out (the halo reads forbid
+ * in-place operation); RR_EWORKSPACE: a workspace smaller than the query; both
+ * before any launch. */
+size_t rr_distort_ragged_workspace(int n, int c, int max_h, int max_w);
+int rr_distort_ragged_u8(int n, int c, int mode, int max_h, int max_w,
+                         const uint8_t *in, size_t in_bytes, const rr_ragged_image *images_dev,
+                         uint8_t *out, const rr_distort_param *params_dev, const float *taps_dev,
+                         const int *tap_idx_dev, const double *noise, unsigned long long seed,
+                         void *workspace, size_t workspace_bytes, rr_stream stream);
+/* 14:31-64 with the draws made on device, as rr_distort_random_u8 makes them:
+ * image i of (seed, *step_dev) draws the same parameters, table index and
+ * noise seed as there, whatever its size; *step_dev advances once per call
+ * (14:75-93 per image, here per batch). */
+int rr_distort_random_ragged_u8(int n, int c, int max_h, int max_w,
+                                const uint8_t *in, size_t in_bytes,
+                                const rr_ragged_image *images_dev, uint8_t *out,
+                                unsigned long long seed, long long *step_dev, const float *table_dev,
+                                void *workspace, size_t workspace_bytes, rr_stream stream);
+/* byte offsets of that call's draws in its workspace, as rr_distort_random_draws
+ * (tests; 14:36-58's draws) */
+int rr_distort_random_ragged_draws(int n, int c, int max_h, int max_w, const void *workspace,
+                                   size_t *params_off, size_t *index_off, size_t *seed_off);
+
 /* running loss on device: acc[0] += x[0] (fp64), count[0] += 1 -- the
  * reference's per-step `running_loss += loss.item()` (14:246) without a host
  * sync; read acc / count once per epoch */
