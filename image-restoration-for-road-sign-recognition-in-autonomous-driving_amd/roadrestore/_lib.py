@@ -213,6 +213,9 @@ _SIGS = {
     "rr_adaptive_avgpool_flatten": (I_, [I_, I_, I_, I_, I_, I_, I_, P_, P_, P_]),
     "rr_resize_workspace": (S_, [I_, I_, I_, I_, I_, I_]),
     "rr_cv_resize_linear_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, P_, I_, P_]),
+    "rr_cv_resize_ragged_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, S_, P_, P_, I_, P_]),
+    "rr_eval_ragged_workspace": (S_, [I_, I_, I_, I_]),
+    "rr_eval_ragged_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, S_, P_, P_, P_, P_, I_, P_, S_, P_]),
     "rr_resize_bilinear_u8": (I_, [I_, I_, I_, I_, I_, I_, P_, I_, P_, P_, P_, P_, S_, P_]),
     "rr_ragged_check": (I_, [I_, I_, S_, P_, I_, I_, I_, I_]),
     "rr_resize_ragged_workspace": (S_, [I_, I_, I_, I_, I_, I_]),

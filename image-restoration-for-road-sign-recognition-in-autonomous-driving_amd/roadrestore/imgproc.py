@@ -17,6 +17,10 @@ DataLoader workers and in the inference loop).  Here they take a whole
 * ``cv_resize`` -- ``cv2.resize(img, (224, 224))`` of the 08 PSNR leg's
   clean image (08:118-119): OpenCV's INTER_LINEAR, which is not PIL's.
 * ``psnr`` / ``ssim`` -- 08:123-125 (skimage semantics, data_range 255).
+* ``restoration_quality`` -- the whole metric leg 08:118-125 for a batch:
+  clean originals of unequal size (a ``RaggedBatch``; ``cv_resize`` and
+  ``RaggedBatch.cv_resize`` take one too) against the restored batch, PSNR
+  and SSIM in one fused call of two launches.
 * ``RaggedBatch`` / ``read_ppm`` / ``ImageFolder`` / ``find_images`` -- the
   step before the first tensor: GTSRB's ``.ppm`` files have unequal sizes and
   the reference resizes each on its own (05:24-32, 14:68, 18:28-36).  A
@@ -51,7 +55,7 @@ __all__ = ["Resize", "ToTensor", "Normalize", "Compose", "apply_random_distortio
            "encode_png", "write_png",
            "RandomDistortion", "motion_blur_table", "DynamicDistortionDataset",
            "apply_compound_distortion", "distortion_params", "psnr", "ssim", "cv_resize",
-           "RaggedBatch", "read_ppm", "read_png", "read_images", "ImageFolder", "find_images",
+           "restoration_quality", "RaggedBatch", "read_ppm", "read_png", "read_images", "ImageFolder", "find_images",
            "IMAGENET_MEAN", "IMAGENET_STD"]
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)      # 18:31
@@ -258,6 +262,13 @@ class RaggedBatch:
             raise ValueError(f"Normalize: {len(mean)} means for {self.channels} channels")
         return ops.resize_ragged_u8(self.data, self.table, self.max_hw, self.channels, oh, ow,
                                     out=out, mean=mean, std=std)
+
+    def cv_resize(self, size):
+        """every image through ``cv2.resize(img, (w, h))`` (INTER_LINEAR,
+        08:118-119), ``size`` = (w, h) in cv2's order: the dense [n, h, w, c]
+        uint8 batch, in one launch (ops.cv_resize_ragged_u8)"""
+        ow, oh = size
+        return ops.cv_resize_ragged_u8(self.data, self.table, self.max_hw, self.channels, oh, ow)
 
 
 _PPM_WS = b" \t\n\r\x0b\x0c"
@@ -758,7 +769,11 @@ def cv_resize(x, size):
     """``cv2.resize(img, (w, h))`` (default INTER_LINEAR) of an [n, h, w, c]
     uint8 device batch (c <= 4): the clean image of the 08 PSNR leg
     (08:118-119; OpenCV's fixed-point bilinear, not PIL's, see
-    rr_cv_resize_linear_u8).  ``size`` = (w, h) in cv2's order."""
+    rr_cv_resize_linear_u8).  ``size`` = (w, h) in cv2's order.  A
+    ``RaggedBatch`` is resized image by image, each from its own size, in one
+    launch (``RaggedBatch.cv_resize``)."""
+    if isinstance(x, RaggedBatch):
+        return x.cv_resize(size)
     _check_u8(x)
     ow, oh = size
     n, h, w, c = x.shape
@@ -777,6 +792,44 @@ def psnr(a, b):
 def ssim(a, b):
     """per-image SSIM (08:125, data_range 255, channel_axis=2)"""
     return ops.ssim_u8(a, b)
+
+
+def restoration_quality(clean, restored):
+    """The metric leg of the 08 loop for a batch (08:118-125) -> ``(psnr,
+    ssim)``, fp64 [n] each, of every restored image against its clean original.
+
+    ``restored``: [n, oh, ow, c] uint8 device tensor (``rr_to_uint8_hwc``'s
+    layout).  ``clean``: a ``RaggedBatch`` of the n originals at their own
+    sizes -- each is put through ``cv2.resize(clean, (ow, oh))`` (08:118-119)
+    and compared in one fused call of two launches, the resized clean images
+    never written to memory (``ops.eval_ragged_u8``) -- or a dense uint8 tensor
+    of ``restored``'s shape, compared as it is by ``psnr`` and ``ssim``.
+
+    The two arguments must share one channel order (08 compares BGR with BGR;
+    RGB with RGB gives the same PSNR, and an SSIM whose channel mean differs in
+    the last bit at most).  Anything else raises ``TypeError``; a batch or
+    channel count that differs between the two raises ``ValueError``."""
+    if (not isinstance(restored, torch.Tensor) or restored.dtype != torch.uint8 or restored.dim() != 4
+            or not restored.is_cuda):
+        raise TypeError("restoration_quality: restored must be an [n, oh, ow, c] uint8 device tensor")
+    if isinstance(clean, RaggedBatch):
+        if not clean.data.is_cuda:
+            raise TypeError("restoration_quality: the clean RaggedBatch must lie on the device")
+        if len(clean) != restored.shape[0] or clean.channels != restored.shape[3]:
+            raise ValueError(f"restoration_quality: {len(clean)} clean images of {clean.channels} channels "
+                             f"against restored {tuple(restored.shape)}")
+        return ops.eval_ragged_u8(clean.data, clean.table, clean.max_hw, clean.channels, restored)
+    if (not isinstance(clean, torch.Tensor) or clean.dtype != torch.uint8 or clean.dim() != 4
+            or not clean.is_cuda):
+        raise TypeError("restoration_quality: clean must be a RaggedBatch or an [n, oh, ow, c] uint8 "
+                        "device tensor")
+    if clean.shape[0] != restored.shape[0] or clean.shape[3] != restored.shape[3]:
+        raise ValueError(f"restoration_quality: clean {tuple(clean.shape)} against restored "
+                         f"{tuple(restored.shape)}")
+    if clean.shape != restored.shape:
+        raise TypeError(f"restoration_quality: a dense clean batch must have restored's shape "
+                        f"{tuple(restored.shape)}, not {tuple(clean.shape)} (pass a RaggedBatch to resize)")
+    return psnr(clean, restored), ssim(clean, restored)
 
 
 # ---------------------------------------------------------------------------

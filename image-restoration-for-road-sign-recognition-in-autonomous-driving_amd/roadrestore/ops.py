@@ -25,7 +25,7 @@ __all__ = [
     "motion_blur_kernel", "first_conv_wgrad_act", "affine_act_pool", "nearest_resize",
     "nearest_resize_bwd", "fold_conv_bn", "bn_stats", "linear_wgrad", "linear_dgrad",
     "dropout_fwd", "dropout_bwd", "dropout_mask", "cross_entropy", "softmax_max", "sgd_",
-    "resize_ragged_u8", "png_unfilter", "distort_ragged_u8",
+    "resize_ragged_u8", "png_unfilter", "distort_ragged_u8", "cv_resize_ragged_u8", "eval_ragged_u8",
 ]
 
 
@@ -1178,6 +1178,72 @@ def resize_ragged_u8(data, table, max_hw, c, oh, ow, out="u8", mean=None, std=No
                                   C.cast(sp, C.c_void_p) if sp is not None else None,
                                   _p(y), _p(ws), wsb, stream()), "rr_resize_ragged_u8")
     return y
+
+
+def _ragged_args(what, data, table, max_hw, c):
+    """the argument checks the ragged image ops share -> (n, c, max_h, max_w)"""
+    for t in (data, table):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} expects torch tensors")
+    _need_cuda(data, table)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise TypeError(f"{what} expects a contiguous 1-D uint8 buffer")
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous():
+        raise TypeError(f"{what} expects an [n, 16] uint8 table of rr_ragged_image records")
+    n, c = int(table.shape[0]), int(c)
+    max_h, max_w = int(max_hw[0]), int(max_hw[1])
+    if n < 1 or not 1 <= c <= 4 or max_h < 1 or max_w < 1 or data.numel() < 1:
+        raise ValueError(f"{what}: n={n} c={c} max={max_h, max_w} buffer of {data.numel()} bytes")
+    return n, c, max_h, max_w
+
+
+def cv_resize_ragged_u8(data, table, max_hw, c, oh, ow):
+    """``cv2.resize(img, (ow, oh))`` (INTER_LINEAR) of n images of unequal
+    size (each clean original of the 08 loop on its own, 08:118-119) into one
+    dense [n, oh, ow, c] uint8 batch, in one launch.  ``data``, ``table``,
+    ``max_hw``: as resize_ragged_u8.  A record that fails rr_ragged_check
+    yields zeros, never an out-of-bounds read."""
+    n, c, max_h, max_w = _ragged_args("cv_resize_ragged_u8", data, table, max_hw, c)
+    oh, ow = int(oh), int(ow)
+    if oh < 1 or ow < 1 or oh * ow * c > 2 ** 31 - 1:
+        raise ValueError(f"cv_resize_ragged_u8: target {(oh, ow)}")
+    y = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=data.device)
+    L = lib()
+    L.check(L.rr_cv_resize_ragged_u8(n, c, max_h, max_w, oh, ow, _p(data), data.numel(), _p(table), _p(y), 0,
+                                     stream()), "rr_cv_resize_ragged_u8")
+    return y
+
+
+def eval_ragged_u8(data, table, max_hw, c, restored):
+    """per-image PSNR and SSIM (08:123-125) of ``cv2.resize(clean_i, (ow,
+    oh))`` (08:118-119) against ``restored`` [n, oh, ow, c] uint8, for n clean
+    images of unequal size (``data``, ``table``, ``max_hw``: as
+    resize_ragged_u8) -> (psnr, ssim), fp64 [n] each.  Two launches; the
+    resized clean images are never written to memory.  A record that fails
+    rr_ragged_check gets NaN for both."""
+    n, c, max_h, max_w = _ragged_args("eval_ragged_u8", data, table, max_hw, c)
+    if not isinstance(restored, torch.Tensor) or restored.dtype != torch.uint8 or restored.dim() != 4:
+        raise TypeError("eval_ragged_u8 expects restored as an [n, oh, ow, c] uint8 tensor")
+    _need_cuda(restored)
+    if restored.device != data.device:
+        raise ValueError("eval_ragged_u8: restored lies on another device than the clean batch")
+    if restored.shape[0] != n or restored.shape[3] != c:
+        raise ValueError(f"eval_ragged_u8: restored {tuple(restored.shape)} for {n} clean images of {c} channels")
+    oh, ow = int(restored.shape[1]), int(restored.shape[2])
+    if oh < 7 or ow < 7:
+        raise ValueError(f"eval_ragged_u8: SSIM's 7 x 7 window exceeds the {oh} x {ow} images")
+    if oh * ow * c > 2 ** 31 - 1:
+        raise ValueError(f"eval_ragged_u8: target {(oh, ow)}")
+    restored = restored.contiguous()
+    L = lib()
+    wsb = L.rr_eval_ragged_workspace(n, c, oh, ow)
+    if wsb == 0:
+        raise RuntimeError(f"rr_eval_ragged_u8: unsupported batch n={n} c={c} -> {(oh, ow)}")
+    ws = _ws(wsb, data.device)
+    out = torch.empty((2, n), dtype=torch.float64, device=data.device)
+    L.check(L.rr_eval_ragged_u8(n, c, max_h, max_w, oh, ow, _p(data), data.numel(), _p(table), _p(restored),
+                                _p(out[0]), _p(out[1]), 0, _p(ws), wsb, stream()), "rr_eval_ragged_u8")
+    return out[0], out[1]
 
 
 def png_unfilter(data, table, max_hw, out_bytes, out=None):

@@ -769,6 +769,42 @@ int rr_cv_resize_linear_u8(int n, int h, int w, int c, int oh, int ow,
                            const uint8_t *in, uint8_t *out, int simd_lanes,
                            rr_stream stream);
 
+/* The same cv2.resize for a ragged batch (rr_ragged_image table, as
+ * rr_resize_ragged_u8 takes it): the 08 loop loads every clean GTSRB original
+ * at its own size and resizes it on its own (08_run_inference.py:118-119).
+ * Every image goes to oh x ow into the dense [n][oh][ow][c] uint8 batch; the
+ * scale is the image's own, 1 / ((double)ow / w) as above; an image already
+ * oh x ow is copied.  One launch, no workspace, the table read on the device
+ * only (graph-capturable).  A record outside [1, max_h] x [1, max_w] or whose
+ * bytes leave [0, in_bytes) is not read and its output is zeros.  RR_EINVAL
+ * before any launch for null pointers, n, sizes <= 0, c outside 1..4, an odd
+ * simd_lanes, in_bytes 0 or above INT64_MAX, or oh * ow * c above INT32_MAX. */
+int rr_cv_resize_ragged_u8(int n, int c, int max_h, int max_w, int oh, int ow,
+                           const uint8_t *in, size_t in_bytes,
+                           const rr_ragged_image *images_dev,
+                           uint8_t *out, int simd_lanes, rr_stream stream);
+
+/* The metric leg of the 08 loop for a batch (08_run_inference.py:123-125):
+ * psnr[i] and ssim[i] (rr_psnr_u8's and rr_ssim_u8's quantities, fp64) of
+ * cv2.resize(clean_i, (ow, oh)) -- clean_i image i of the ragged buffer,
+ * resized as rr_cv_resize_ragged_u8 does, 08:118-119 -- against restored_i of
+ * the dense [n][oh][ow][c] uint8 batch.  Two launches whatever n is; the
+ * resized clean image is never written to memory; no atomics, sums in a fixed
+ * order: results are identical from run to run.  Both batches must share one
+ * channel order.  workspace (8-byte aligned): one partial record per 32 x 32
+ * block of output pixels per image.  RR_EINVAL for oh or ow below 7 (skimage's
+ * win_size error; the workspace query returns 0) and for the bad arguments of
+ * rr_cv_resize_ragged_u8, RR_EWORKSPACE for a short workspace, all before any
+ * launch.  A record that fails the table test gets psnr = ssim = NaN and is
+ * not read.  No host synchronisation: graph-capturable. */
+size_t rr_eval_ragged_workspace(int n, int c, int oh, int ow);
+int rr_eval_ragged_u8(int n, int c, int max_h, int max_w, int oh, int ow,
+                      const uint8_t *clean, size_t clean_bytes,
+                      const rr_ragged_image *images_dev,
+                      const uint8_t *restored, double *psnr, double *ssim,
+                      int simd_lanes, void *workspace, size_t workspace_bytes,
+                      rr_stream stream);
+
 /* skimage structural_similarity(a, b, data_range=255, channel_axis=2)
  * (08_run_inference.py:125) per image of [n][h][w][c] uint8, fp64 out[n] */
 size_t rr_ssim_workspace(int n, int c);
