@@ -1,5 +1,5 @@
 // philox.h -- the Philox4x32-10 generator shared by the image distortions
-// (imgproc.hip) and training-mode dropout (linear.hip).
+// (distort.hip) and training-mode dropout (linear.hip).
 #pragma once
 #include <stdint.h>
 

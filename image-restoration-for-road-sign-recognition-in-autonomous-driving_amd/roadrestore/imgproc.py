@@ -3,7 +3,7 @@
 The reference runs these per image on the host (cv2 / PIL / skimage in
 DataLoader workers and in the inference loop).  Here they take a whole
 [n, h, w, c] uint8 batch resident on the GPU and run as HIP kernels
-(csrc/imgproc.hip) behind the C ABI:
+(csrc/resize.hip, quality.hip, distort.hip) behind the C ABI:
 
 * ``Resize`` / ``ToTensor`` / ``Normalize`` / ``Compose`` -- torchvision's
   transform names and argument meaning (17:66, 18:28-32); ``Resize`` is
@@ -304,6 +304,22 @@ def _ppm_header(head, path):
     return vals[0], vals[1], vals[2], pos + 1
 
 
+def _read_ppm_file(path, buf, a, b):
+    """one binary PPM file into buf[a:b] -> (byte offset of the pixels in the file, h, w);
+    ValueError naming the file unless it is an 8-bit P6 with all its pixels"""
+    with open(path, "rb") as f:
+        got = f.readinto(memoryview(buf[a:b])) if b > a else 0
+    w, h, maxval, off = _ppm_header(bytes(buf[a:a + min(got, _PPM_HEAD)]), path)
+    if not 1 <= maxval <= 255:
+        raise ValueError(f"{path}: maxval {maxval}: only 8-bit PPM (maxval <= 255) is read")
+    if h < 1 or w < 1 or h > 2 ** 31 - 1 or w > 2 ** 31 - 1:
+        raise ValueError(f"{path}: bad PPM size {w} x {h}")
+    if off + h * w * 3 > got:
+        raise ValueError(f"{path}: truncated PPM: {w} x {h} needs {h * w * 3} pixel bytes, "
+                         f"{max(got - off, 0)} present")
+    return off, h, w
+
+
 def read_ppm(paths, device, threads=0):
     """Binary PPM files (P6, maxval <= 255: what GTSRB ships) -> RaggedBatch on
     ``device``.  The whole files are read by a thread pool into one host
@@ -326,17 +342,8 @@ def read_ppm(paths, device, threads=0):
     rec = np.zeros(n, dtype=_RECORD)
 
     def one(i):
-        a, b = int(start[i]), int(start[i] + fsize[i])
-        with open(paths[i], "rb") as f:
-            got = f.readinto(memoryview(buf[a:b])) if b > a else 0
-        w, h, maxval, off = _ppm_header(bytes(buf[a:a + min(got, _PPM_HEAD)]), paths[i])
-        if not 1 <= maxval <= 255:
-            raise ValueError(f"{paths[i]}: maxval {maxval}: only 8-bit PPM (maxval <= 255) is read")
-        if h < 1 or w < 1 or h > 2 ** 31 - 1 or w > 2 ** 31 - 1:
-            raise ValueError(f"{paths[i]}: bad PPM size {w} x {h}")
-        if off + h * w * 3 > got:
-            raise ValueError(f"{paths[i]}: truncated PPM: {w} x {h} needs {h * w * 3} pixel bytes, "
-                             f"{max(got - off, 0)} present")
+        a = int(start[i])
+        off, h, w = _read_ppm_file(paths[i], buf, a, a + int(fsize[i]))
         rec[i] = (a + off, h, w)
 
     workers = int(threads) if threads else min(8, n)
@@ -399,17 +406,8 @@ def _stage_files(paths, is_png, device, threads):
     rec["src"] = start
 
     def one_ppm(i):
-        a, b = int(start[i]), int(start[i] + slot[i])
-        with open(paths[i], "rb") as f:
-            got = f.readinto(memoryview(buf[a:b])) if b > a else 0
-        w, h, maxval, off = _ppm_header(bytes(buf[a:a + min(got, _PPM_HEAD)]), paths[i])
-        if not 1 <= maxval <= 255:
-            raise ValueError(f"{paths[i]}: maxval {maxval}: only 8-bit PPM (maxval <= 255) is read")
-        if h < 1 or w < 1 or h > 2 ** 31 - 1 or w > 2 ** 31 - 1:
-            raise ValueError(f"{paths[i]}: bad PPM size {w} x {h}")
-        if off + h * w * 3 > got:
-            raise ValueError(f"{paths[i]}: truncated PPM: {w} x {h} needs {h * w * 3} pixel bytes, "
-                             f"{max(got - off, 0)} present")
+        a = int(start[i])
+        off, h, w = _read_ppm_file(paths[i], buf, a, a + int(slot[i]))
         rec[i] = (a + off, 0, h, w, 3, 0)
 
     if workers <= 1 or len(ppm) <= 1:
@@ -607,7 +605,6 @@ def motion_blur_table(device):
     key = str(device)
     t = _TABLES.get(key)
     if t is None:
-        import ctypes as C
         L = ops.lib()
         nf = L.rr_motion_blur_table_floats()
         host = torch.empty(nf, dtype=torch.float32)
@@ -642,18 +639,10 @@ class RandomDistortion:
         _check_u8(x)
         ops._need_cuda(x)
         n, h, w, c = x.shape
-        x = x.contiguous()
-        L = ops.lib()
         if self._ws is None or self._shape != (n, h, w, c):
-            self._ws = ops._ws(L.rr_distort_random_workspace(n, h, w, c), self.device)
+            self._ws = ops._ws(lib().rr_distort_random_workspace(n, h, w, c), self.device)
             self._shape = (n, h, w, c)
-        if out is None:
-            out = torch.empty_like(x)
-        L.check(L.rr_distort_random_u8(n, h, w, c, x.data_ptr(), out.data_ptr(), self.seed,
-                                       self.step.data_ptr(), self.table.data_ptr(),
-                                       self._ws.data_ptr(), self._ws.numel(), ops.stream()),
-                "rr_distort_random_u8")
-        return out
+        return ops.distort_random_u8(x, self.seed, self.step, self.table, self._ws, out)
 
     def _ragged(self, x, out):
         """a RaggedBatch: every image at its native size, as 14:75-93 distorts
@@ -662,35 +651,25 @@ class RandomDistortion:
         what image i of a dense batch draws at the same (seed, step)."""
         ops._need_cuda(x.data, x.table)
         n, c, (max_h, max_w) = len(x), x.channels, x.max_hw
-        L = ops.lib()
         shape = ("ragged", n, c, max_h, max_w)
         if self._ws is None or self._shape != shape:
-            self._ws = ops._ws(L.rr_distort_ragged_workspace(n, c, max_h, max_w), self.device)
+            self._ws = ops._ws(lib().rr_distort_ragged_workspace(n, c, max_h, max_w), self.device)
             self._shape = shape
         if out is None:
             out = torch.empty_like(x.data)
         y = x.with_data(out)                            # checks out against the batch's buffer
-        L.check(L.rr_distort_random_ragged_u8(n, c, max_h, max_w, x.data.data_ptr(), x.data.numel(),
-                                              x.table.data_ptr(), out.data_ptr(), self.seed,
-                                              self.step.data_ptr(), self.table.data_ptr(),
-                                              self._ws.data_ptr(), self._ws.numel(), ops.stream()),
-                "rr_distort_random_ragged_u8")
+        ops.distort_random_ragged_u8(x.data, x.table, x.max_hw, c, self.seed, self.step, self.table,
+                                     self._ws, out)
         return y
 
     def last_draws(self):
         """-> (params: list of DistortParam, table index [n] int32, noise seed)"""
-        import ctypes as C
         po, io, so = C.c_size_t(), C.c_size_t(), C.c_size_t()
-        L = ops.lib()
-        if self._shape[0] == "ragged":
-            _, n, c, max_h, max_w = self._shape
-            L.check(L.rr_distort_random_ragged_draws(n, c, max_h, max_w, self._ws.data_ptr(), C.byref(po),
-                                                     C.byref(io), C.byref(so)),
-                    "rr_distort_random_ragged_draws")
-        else:
-            n, h, w, c = self._shape
-            L.check(L.rr_distort_random_draws(n, h, w, c, self._ws.data_ptr(), C.byref(po), C.byref(io),
-                                              C.byref(so)), "rr_distort_random_draws")
+        ragged = self._shape[0] == "ragged"
+        dims = self._shape[1:] if ragged else self._shape          # (n, c, max_h, max_w) or (n, h, w, c)
+        name = "rr_distort_random_ragged_draws" if ragged else "rr_distort_random_draws"
+        lib().check(getattr(lib(), name)(*dims, self._ws.data_ptr(), C.byref(po), C.byref(io), C.byref(so)), name)
+        n = dims[0]
         raw = self._ws.cpu()
         sz = C.sizeof(DistortParam)
         arr = (DistortParam * n).from_buffer_copy(bytes(raw[po.value:po.value + n * sz].numpy()))
@@ -776,12 +755,7 @@ def cv_resize(x, size):
         return x.cv_resize(size)
     _check_u8(x)
     ow, oh = size
-    n, h, w, c = x.shape
-    x = x.contiguous()
-    out = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=x.device)
-    lib().check(lib().rr_cv_resize_linear_u8(n, h, w, c, oh, ow, x.data_ptr(), out.data_ptr(),
-                                              0, ops.stream()), "rr_cv_resize_linear_u8")
-    return out
+    return ops.cv_resize_linear_u8(x, oh, ow)
 
 
 def psnr(a, b):

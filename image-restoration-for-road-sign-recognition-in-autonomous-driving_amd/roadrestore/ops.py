@@ -26,6 +26,7 @@ __all__ = [
     "nearest_resize_bwd", "fold_conv_bn", "bn_stats", "linear_wgrad", "linear_dgrad",
     "dropout_fwd", "dropout_bwd", "dropout_mask", "cross_entropy", "softmax_max", "sgd_",
     "resize_ragged_u8", "png_unfilter", "distort_ragged_u8", "cv_resize_ragged_u8", "eval_ragged_u8",
+    "cv_resize_linear_u8", "distort_random_u8", "distort_random_ragged_u8",
 ]
 
 
@@ -1118,28 +1119,41 @@ def resize_bilinear_u8(x, oh, ow, out="u8", mean=None, std=None):
         raise TypeError("resize_bilinear_u8 expects a [n, h, w, c] uint8 tensor")
     n, h, w, c = x.shape
     x = x.contiguous()
-    if out == "u8":
-        y = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=x.device)
-        kind = 0
-    elif out == "f32":
-        y = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
-        kind = 1
-    else:
-        raise ValueError(out)
+    kind, y = _resize_out(out, n, c, oh, ow, x.device)
     L = lib()
     wsb = L.rr_resize_workspace(n, h, w, c, oh, ow)
     if wsb == 0:
         raise RuntimeError(f"rr_resize_bilinear_u8: unsupported shape {tuple(x.shape)} -> {(oh, ow)}")
     ws = _ws(wsb, x.device)
-    mp = sp = None
-    if mean is not None:
-        mp = (C.c_float * c)(*[float(v) for v in mean])
-        sp = (C.c_float * c)(*[float(v) for v in std])
-    L.check(L.rr_resize_bilinear_u8(n, h, w, c, oh, ow, _p(x), kind,
-                                    C.cast(mp, C.c_void_p) if mp is not None else None,
-                                    C.cast(sp, C.c_void_p) if sp is not None else None,
+    L.check(L.rr_resize_bilinear_u8(n, h, w, c, oh, ow, _p(x), kind, *_norm_ptrs(mean, std, c),
                                     _p(y), _p(ws), wsb, stream()), "rr_resize_bilinear_u8")
     return y
+
+
+def _resize_out(out, n, c, oh, ow, device):
+    """out="u8" / "f32" -> (out_kind, the empty NHWC uint8 / NCHW fp32 result)"""
+    if out not in ("u8", "f32"):
+        raise ValueError(out)
+    if out == "u8":
+        return 0, torch.empty((n, oh, ow, c), dtype=torch.uint8, device=device)
+    return 1, torch.empty((n, c, oh, ow), dtype=torch.float32, device=device)
+
+
+def _norm_ptrs(mean, std, c):
+    """Normalize's constants as the C calls' two float[c] (null, null without a mean)"""
+    if mean is None:
+        return None, None
+    return tuple(C.cast((C.c_float * c)(*[float(v) for v in a]), C.c_void_p) for a in (mean, std))
+
+
+def _ragged_tensors(what, data, table, *also_on_device):
+    """the tensor checks every ragged image op makes -> n"""
+    _need_cuda(data, table, *also_on_device)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise TypeError(f"{what} expects a contiguous 1-D uint8 buffer")
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous():
+        raise TypeError(f"{what} expects an [n, 16] uint8 table of rr_ragged_image records")
+    return int(table.shape[0])
 
 
 def resize_ragged_u8(data, table, max_hw, c, oh, ow, out="u8", mean=None, std=None):
@@ -1151,50 +1165,46 @@ def resize_ragged_u8(data, table, max_hw, c, oh, ow, out="u8", mean=None, std=No
     max_w) bounding every image.  out="u8": [n, oh, ow, c] uint8; out="f32":
     [n, c, oh, ow] fp32 ToTensor (+ Normalize(mean, std)).  A record that fails
     rr_ragged_check yields zeros, never an out-of-bounds read."""
-    _need_cuda(data, table)
-    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
-        raise TypeError("resize_ragged_u8 expects a contiguous 1-D uint8 buffer")
-    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous():
-        raise TypeError("resize_ragged_u8 expects an [n, 16] uint8 table of rr_ragged_image records")
-    n, c = int(table.shape[0]), int(c)
+    n, c = _ragged_tensors("resize_ragged_u8", data, table), int(c)
     max_h, max_w = int(max_hw[0]), int(max_hw[1])
     oh, ow = int(oh), int(ow)
     if out not in ("u8", "f32"):
         raise ValueError(out)
-    kind = 0 if out == "u8" else 1
     L = lib()
     wsb = L.rr_resize_ragged_workspace(n, c, max_h, max_w, oh, ow)
     if wsb == 0:
         raise RuntimeError(f"rr_resize_ragged_u8: unsupported batch n={n} c={c} max={max_h, max_w} -> {(oh, ow)}")
-    y = torch.empty((n, oh, ow, c) if kind == 0 else (n, c, oh, ow),
-                    dtype=torch.uint8 if kind == 0 else torch.float32, device=data.device)
+    kind, y = _resize_out(out, n, c, oh, ow, data.device)
     ws = _ws(wsb, data.device)
-    mp = sp = None
-    if mean is not None:
-        mp = (C.c_float * c)(*[float(v) for v in mean])
-        sp = (C.c_float * c)(*[float(v) for v in std])
     L.check(L.rr_resize_ragged_u8(n, c, max_h, max_w, oh, ow, _p(data), data.numel(), _p(table), kind,
-                                  C.cast(mp, C.c_void_p) if mp is not None else None,
-                                  C.cast(sp, C.c_void_p) if sp is not None else None,
-                                  _p(y), _p(ws), wsb, stream()), "rr_resize_ragged_u8")
+                                  *_norm_ptrs(mean, std, c), _p(y), _p(ws), wsb, stream()),
+            "rr_resize_ragged_u8")
     return y
 
 
 def _ragged_args(what, data, table, max_hw, c):
-    """the argument checks the ragged image ops share -> (n, c, max_h, max_w)"""
+    """_ragged_tensors and the range checks of the two cv2-side ops -> (n, c, max_h, max_w)"""
     for t in (data, table):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{what} expects torch tensors")
-    _need_cuda(data, table)
-    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
-        raise TypeError(f"{what} expects a contiguous 1-D uint8 buffer")
-    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous():
-        raise TypeError(f"{what} expects an [n, 16] uint8 table of rr_ragged_image records")
-    n, c = int(table.shape[0]), int(c)
+    n, c = _ragged_tensors(what, data, table), int(c)
     max_h, max_w = int(max_hw[0]), int(max_hw[1])
     if n < 1 or not 1 <= c <= 4 or max_h < 1 or max_w < 1 or data.numel() < 1:
         raise ValueError(f"{what}: n={n} c={c} max={max_h, max_w} buffer of {data.numel()} bytes")
     return n, c, max_h, max_w
+
+
+def cv_resize_linear_u8(x, oh, ow):
+    """``cv2.resize(img, (ow, oh))`` (INTER_LINEAR, 08:118-119) of a dense
+    [n, h, w, c] uint8 batch (c <= 4) -> [n, oh, ow, c] uint8"""
+    _need_cuda(x)
+    if x.dtype != torch.uint8 or x.dim() != 4:
+        raise TypeError("cv_resize_linear_u8 expects a [n, h, w, c] uint8 tensor")
+    n, h, w, c = x.shape
+    y = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=x.device)
+    lib().check(lib().rr_cv_resize_linear_u8(n, h, w, c, oh, ow, _p(x.contiguous()), _p(y), 0, stream()),
+                "rr_cv_resize_linear_u8")
+    return y
 
 
 def cv_resize_ragged_u8(data, table, max_hw, c, oh, ow):
@@ -1302,13 +1312,8 @@ def distort_u8(x, params, taps, mode=0, noise=None, seed=0):
     _need_cuda(x)
     n, h, w, c = x.shape
     x = x.contiguous()
-    if len(params) != n:
-        raise ValueError("one DistortParam per image")
-    arr = (DistortParam * n)(*params)
-    prm = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(x.device)
-    taps = taps.to(x.device, torch.float32).contiguous()
-    if tuple(taps.shape) != (n, RR_DISTORT_KMAX, RR_DISTORT_KMAX):
-        raise ValueError("taps must be [n, KMAX, KMAX]")
+    prm = _params_dev(params, n, x.device)
+    taps = _taps_dev(taps, n, x.device)
     if noise is not None:
         noise = noise.to(x.device, torch.float64).contiguous()
         if tuple(noise.shape) != (n, h, w, c):
@@ -1320,6 +1325,39 @@ def distort_u8(x, params, taps, mode=0, noise=None, seed=0):
     L.check(L.rr_distort_u8(n, h, w, c, int(mode), _p(x), _p(y), _p(prm), _p(taps), _p(noise),
                             int(seed) & (2 ** 64 - 1), _p(ws), wsb, stream()), "rr_distort_u8")
     return y
+
+
+def _params_dev(params, n, device):
+    """n DistortParam -> their bytes on the device (n rr_distort_param)"""
+    if len(params) != n:
+        raise ValueError("one DistortParam per image")
+    return torch.frombuffer(bytearray((DistortParam * n)(*params)), dtype=torch.uint8).to(device)
+
+
+def _taps_dev(taps, n_required, device):
+    """-> fp32 [m, KMAX, KMAX] on the device; m == n_required unless that is None (a tap_idx picks)"""
+    taps = taps.to(device, torch.float32).contiguous()
+    if (taps.dim() != 3 or tuple(taps.shape[1:]) != (RR_DISTORT_KMAX, RR_DISTORT_KMAX)
+            or n_required not in (None, taps.shape[0])):
+        raise ValueError("taps must be [n, KMAX, KMAX]")
+    return taps
+
+
+def distort_random_u8(x, seed, step, table, ws=None, out=None):
+    """distort_u8 with the per-image draws made on the device from (``seed``, ``step``: int64 device
+    scalar, advanced by one); ``table``: imgproc.motion_blur_table; ``ws``: rr_distort_random_workspace
+    bytes that keep the draws readable (imgproc.RandomDistortion owns one)"""
+    _need_cuda(x, step, table, ws, out)
+    if x.dtype != torch.uint8 or x.dim() != 4:
+        raise TypeError("distort_random_u8 expects a [n, h, w, c] uint8 tensor")
+    n, h, w, c = x.shape
+    x = x.contiguous()
+    L = lib()
+    ws = _ws(L.rr_distort_random_workspace(n, h, w, c), x.device) if ws is None else ws
+    out = torch.empty_like(x) if out is None else out
+    L.check(L.rr_distort_random_u8(n, h, w, c, _p(x), _p(out), int(seed) & (2 ** 64 - 1), _p(step), _p(table),
+                                   _p(ws), ws.numel(), stream()), "rr_distort_random_u8")
+    return out
 
 
 def _ragged_elems(table, params, max_hw, c, in_bytes):
@@ -1350,38 +1388,23 @@ def distort_ragged_u8(data, table, max_hw, c, params, taps, mode=0, noise=None, 
     offset (``out``, when given, is that buffer; no byte outside the images is
     written).  A record that fails rr_ragged_check, or has the blur flag with
     ksize outside [1, KMAX], is skipped: nothing read, nothing written."""
-    _need_cuda(data, table, tap_idx, out)
-    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
-        raise TypeError("distort_ragged_u8 expects a contiguous 1-D uint8 buffer")
-    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous():
-        raise TypeError("distort_ragged_u8 expects an [n, 16] uint8 table of rr_ragged_image records")
-    n, c = int(table.shape[0]), int(c)
+    n, c = _ragged_tensors("distort_ragged_u8", data, table, tap_idx, out), int(c)
     max_h, max_w = int(max_hw[0]), int(max_hw[1])
-    if len(params) != n:
-        raise ValueError("one DistortParam per image")
     if mode not in (0, 1):
         raise ValueError(mode)
-    arr = (DistortParam * n)(*params)
-    prm = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(data.device)
-    taps = taps.to(data.device, torch.float32).contiguous()
-    if taps.dim() != 3 or tuple(taps.shape[1:]) != (RR_DISTORT_KMAX, RR_DISTORT_KMAX):
-        raise ValueError("taps must be [n, KMAX, KMAX]")
-    if tap_idx is None:
-        if taps.shape[0] != n:
-            raise ValueError("taps must be [n, KMAX, KMAX]")
-    elif tap_idx.dtype != torch.int32 or tuple(tap_idx.shape) != (n,) or not tap_idx.is_contiguous():
+    prm = _params_dev(params, n, data.device)
+    taps = _taps_dev(taps, n if tap_idx is None else None, data.device)
+    if tap_idx is not None and (tap_idx.dtype != torch.int32 or tuple(tap_idx.shape) != (n,)
+                                or not tap_idx.is_contiguous()):
         raise TypeError("tap_idx must be a contiguous int32 [n] device tensor")
     if noise is not None:
         noise = noise.to(data.device, torch.float64).contiguous()
         need = _ragged_elems(table, params, (max_h, max_w), c, data.numel())
         if noise.dim() != 1 or noise.numel() < need:
             raise ValueError(f"noise must be a 1-D field of the batch's {need} elements in table order")
-    if out is None:
-        out = torch.empty_like(data)
-    elif (out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
-          or out.numel() != data.numel() or out.data_ptr() == data.data_ptr()):
-        raise TypeError(f"distort_ragged_u8 out: expected another contiguous 1-D uint8 buffer of "
-                        f"{data.numel()} bytes (the blur reads its neighbours: not in place)")
+    if out is not None and out.data_ptr() == data.data_ptr():
+        raise TypeError("distort_ragged_u8 out: the blur reads its neighbours, not in place")
+    out = _ragged_out("distort_ragged_u8", data, out)
     L = lib()
     wsb = L.rr_distort_ragged_workspace(n, c, max_h, max_w)
     if wsb == 0:
@@ -1390,6 +1413,30 @@ def distort_ragged_u8(data, table, max_hw, c, params, taps, mode=0, noise=None, 
     L.check(L.rr_distort_ragged_u8(n, c, int(mode), max_h, max_w, _p(data), data.numel(), _p(table), _p(out),
                                    _p(prm), _p(taps), _p(tap_idx), _p(noise), int(seed) & (2 ** 64 - 1),
                                    _p(ws), wsb, stream()), "rr_distort_ragged_u8")
+    return out
+
+
+def _ragged_out(what, data, out):
+    """the buffer a ragged distortion writes: as long as ``data``, or a new one"""
+    if out is None:
+        return torch.empty_like(data)
+    if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() != data.numel():
+        raise TypeError(f"{what} out: expected a contiguous 1-D uint8 buffer of {data.numel()} bytes")
+    return out
+
+
+def distort_random_ragged_u8(data, table, max_hw, c, seed, step, blur_table, ws=None, out=None):
+    """distort_ragged_u8 with the draws made on the device: image i draws what image i of
+    distort_random_u8 draws at the same (``seed``, ``step``).  ``ws``: rr_distort_ragged_workspace
+    bytes, as distort_random_u8's.  ``out`` must not be ``data``: the library refuses."""
+    n, c = _ragged_tensors("distort_random_ragged_u8", data, table, step, blur_table, ws, out), int(c)
+    max_h, max_w = int(max_hw[0]), int(max_hw[1])
+    out = _ragged_out("distort_random_ragged_u8", data, out)
+    L = lib()
+    ws = _ws(L.rr_distort_ragged_workspace(n, c, max_h, max_w), data.device) if ws is None else ws
+    L.check(L.rr_distort_random_ragged_u8(n, c, max_h, max_w, _p(data), data.numel(), _p(table), _p(out),
+                                          int(seed) & (2 ** 64 - 1), _p(step), _p(blur_table), _p(ws),
+                                          ws.numel(), stream()), "rr_distort_random_ragged_u8")
     return out
 
 

@@ -1,6 +1,6 @@
-"""GPU parity of the image-I/O kernels (csrc/imgproc.hip) against the CPU
-oracle (oracle/imgproc_cpu.py, itself pinned to Pillow in
-test_imgproc_cpu.py): bit-exact for the uint8 / fixed-point work, fp32
+"""GPU parity of the image-I/O kernels (csrc/resize.hip, quality.hip,
+distort.hip) against the CPU oracle (oracle/imgproc_cpu.py, itself pinned to
+Pillow in test_imgproc_cpu.py): bit-exact for the uint8 / fixed-point work, fp32
 ToTensor/Normalize bit-exact, SSIM within 1e-10 (exact integer window sums
 here vs scipy's running fp64 sums in the restatement)."""
 import random

@@ -1,6 +1,6 @@
-"""Throughput of the image-I/O kernels (csrc/imgproc.hip) on one GPU, with
-HIP-event timing on the launch stream, as bytes moved per second (they are
-HBM/L2-bound byte kernels; algorithmic bytes = inputs read once + outputs
+"""Throughput of the image-I/O kernels (csrc/resize.hip, quality.hip,
+distort.hip) on one GPU, with HIP-event timing on the launch stream, as bytes
+moved per second (they are HBM/L2-bound byte kernels; algorithmic bytes = inputs read once + outputs
 written once).  usage: python tools/bench_imgproc.py"""
 import json
 import os
