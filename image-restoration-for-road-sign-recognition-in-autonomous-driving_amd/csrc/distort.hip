@@ -9,6 +9,9 @@
 //   * rr_distort_ragged_u8 / rr_distort_random_ragged_u8: n images of unequal
 //     size in one buffer, each at its native size, in two launches, the blur
 //     input in LDS and no staging image.
+//   * rr_distort_single_ragged_u8: the noise, blur and fog of the offline
+//     generators 02-04 and of 13:33-56 in their own spelling, one kind per
+//     ragged batch; the blur with 03:29's per-image min-max stretch.
 //   * rr_motion_blur_kernel / rr_motion_blur_table: cv2's rotated line kernel
 //     restated on the host, one kernel or all 11 x 361 the draws can pick.
 // The work is VALU (Philox + logf / cosf for the noise, up to 225 taps per
@@ -27,6 +30,7 @@
 #include "imgproc.h"
 #include "philox.h"
 
+#include <cfloat>
 #include <cmath>
 
 namespace {
@@ -368,37 +372,17 @@ __device__ __forceinline__ bool rd_valid(const rr_ragged_image &r, const rr_dist
   return rg_valid(r, c, max_h, max_w, in_bytes);
 }
 
-// draw != 0: image i's draws of (seed, *step) into prm_out / idx_out (= a.d.prm
-// / a.d.tap_idx), the step's noise seed, *step += 1 -- distort_draw_kernel's
-// work, by the same device functions
-__global__ __launch_bounds__(256) void rdist_prologue_kernel(RdArgs a, int draw, unsigned long long seed,
-                                                             long long *step, rr_distort_param *prm_out,
-                                                             int *idx_out, unsigned long long *noise_seed) {
+// elem_base[i] = the exclusive prefix sum of count(i) over the n records, by
+// one 256-thread workgroup; count(i), the elements of record i (0 for an
+// invalid one), is called once, by thread i % 256
+template <class Count>
+__device__ __forceinline__ void elem_base_scan(int n, long long *elem_base, Count count) {
   __shared__ long long scan[256];
   const int t = threadIdx.x;
-  long long s = 0;
-  unsigned long long key = 0;
-  if (draw) {
-    s = *step;
-    key = draw_key(seed, s);
-  }
   long long carry = 0;                                      // elements of the records before this chunk
-  for (int i0 = 0; i0 < a.d.n; i0 += 256) {
+  for (int i0 = 0; i0 < n; i0 += 256) {
     const int i = i0 + t;
-    long long v = 0;
-    if (i < a.d.n) {
-      rr_distort_param p;
-      if (draw) {
-        int ti;
-        distort_draw_one(i, key, &p, &ti);
-        prm_out[i] = p;
-        idx_out[i] = ti;
-      } else {
-        p = a.d.prm[i];
-      }
-      const rr_ragged_image r = a.tab[i];
-      if (rd_valid(r, p, a.d.c, a.d.h, a.d.w, a.in_bytes)) v = (long long)r.h * r.w * a.d.c;
-    }
+    const long long v = i < n ? count(i) : 0;
     scan[t] = v;
     __syncthreads();
     for (int o = 1; o < 256; o <<= 1) {                     // inclusive scan of the chunk
@@ -407,13 +391,87 @@ __global__ __launch_bounds__(256) void rdist_prologue_kernel(RdArgs a, int draw,
       scan[t] += u;
       __syncthreads();
     }
-    if (i < a.d.n) a.elem_base[i] = carry + scan[t] - v;
+    if (i < n) elem_base[i] = carry + scan[t] - v;
     carry += scan[255];
     __syncthreads();                                        // scan is rewritten by the next chunk
   }
+}
+
+// draw != 0: image i's draws of (seed, *step) into prm_out / idx_out (= a.d.prm
+// / a.d.tap_idx), the step's noise seed, *step += 1 -- distort_draw_kernel's
+// work, by the same device functions
+__global__ __launch_bounds__(256) void rdist_prologue_kernel(RdArgs a, int draw, unsigned long long seed,
+                                                             long long *step, rr_distort_param *prm_out,
+                                                             int *idx_out, unsigned long long *noise_seed) {
+  const int t = threadIdx.x;
+  long long s = 0;
+  unsigned long long key = 0;
+  if (draw) {
+    s = *step;
+    key = draw_key(seed, s);
+  }
+  elem_base_scan(a.d.n, a.elem_base, [&](int i) -> long long {
+    rr_distort_param p;
+    if (draw) {
+      int ti;
+      distort_draw_one(i, key, &p, &ti);
+      prm_out[i] = p;
+      idx_out[i] = ti;
+    } else {
+      p = a.d.prm[i];
+    }
+    const rr_ragged_image r = a.tab[i];
+    return rd_valid(r, p, a.d.c, a.d.h, a.d.w, a.in_bytes) ? (long long)r.h * r.w * a.d.c : 0;
+  });
   if (draw && t == 0) {
     *noise_seed = draw_noise_seed(key);
     *step = s + 1;
+  }
+}
+
+// a staged pixel takes PS bytes, 4 for 3 channels: the tap loop then reads a
+// pixel in one aligned LDS load (3-byte pixels made it a misaligned 16-bit
+// load plus a byte load per tap, and the tap loop the slowest part of the
+// call by far)
+template <int C> struct TilePix {
+  static constexpr int PS = C == 3 ? 4 : C;
+  using type = std::conditional_t<PS == 4, uint32_t, std::conditional_t<PS == 2, uint16_t, uint8_t>>;
+};
+
+// the nonzero taps of the k x k kernel kt in row-major order (cv2 drops zero
+// taps), listed by the first wave alone (t < 64): tap u = lane + 64 j, so the
+// ballots come in tap order
+__device__ __forceinline__ void list_taps(const float *kt, int k, int t, float *tv, int *ti, int *ntaps) {
+  constexpr int K2 = RR_DISTORT_KMAX * RR_DISTORT_KMAX;
+  int off = 0;
+#pragma unroll
+  for (int j = 0; j < (K2 + 63) / 64; ++j) {
+    const int u = t + 64 * j, ki = u / k, kj = u - ki * k;
+    const float kv = u < k * k ? kt[ki * RR_DISTORT_KMAX + kj] : 0.f;
+    const bool nz = kv != 0.f;
+    const unsigned long long m = __ballot(nz);
+    if (nz) {
+      const int pos = off + __popcll(m & ((1ull << t) - 1ull));
+      tv[pos] = kv;
+      ti[pos] = (ki << 8) | kj;
+    }
+    off += __popcll(m);
+  }
+  if (t == 0) *ntaps = off;
+}
+
+// the fp32 tap sum of one output pixel out of the staged tile (pw pixels a
+// row), base its top-left tap's pixel
+template <int C>
+__device__ __forceinline__ void tap_sum(const typename TilePix<C>::type *base, int pw, int nt, const float *tv,
+                                        const int *ti, float *s) {
+#pragma clang fp contract(off)
+  for (int u = 0; u < nt; ++u) {
+    const int ij = ti[u];
+    const float w = tv[u];
+    const uint32_t px = base[(ij >> 8) * pw + (ij & 255)];
+#pragma unroll
+    for (int c = 0; c < C; ++c) s[c] = s[c] + w * (float)((px >> (8 * c)) & 255u);
   }
 }
 
@@ -421,12 +479,8 @@ template <int C, int TH, int TW>
 __global__ __launch_bounds__(256) void rdist_tile_kernel(RdArgs a) {
 #pragma clang fp contract(off)
   constexpr int K2 = RR_DISTORT_KMAX * RR_DISTORT_KMAX;
-  // a staged pixel takes PS bytes, 4 for 3 channels: the tap loop then reads a
-  // pixel in one aligned LDS load (3-byte pixels made it a misaligned 16-bit
-  // load plus a byte load per tap, and the tap loop the slowest part of the
-  // call by far)
-  constexpr int PS = C == 3 ? 4 : C;
-  using Pix = std::conditional_t<PS == 4, uint32_t, std::conditional_t<PS == 2, uint16_t, uint8_t>>;
+  constexpr int PS = TilePix<C>::PS;
+  using Pix = typename TilePix<C>::type;
   __shared__ Pix simg[(TH + RR_DISTORT_KMAX - 1) * (TW + RR_DISTORT_KMAX - 1)];
   __shared__ float tv[K2];
   __shared__ int ti[K2];
@@ -457,26 +511,7 @@ __global__ __launch_bounds__(256) void rdist_tile_kernel(RdArgs a) {
     return;
   }
   const int k = p.ksize, anc = k / 2;
-  // the nonzero taps in row-major order (cv2 drops zero taps), listed by the
-  // first wave alone: tap u = lane + 64 j, so the ballots come in tap order
-  if (t < 64) {
-    const float *kt = d.taps + (long long)(d.tap_idx ? d.tap_idx[img] : img) * K2;
-    int off = 0;
-#pragma unroll
-    for (int j = 0; j < (K2 + 63) / 64; ++j) {
-      const int u = t + 64 * j, ki = u / k, kj = u - ki * k;
-      const float kv = u < k * k ? kt[ki * RR_DISTORT_KMAX + kj] : 0.f;
-      const bool nz = kv != 0.f;
-      const unsigned long long m = __ballot(nz);
-      if (nz) {
-        const int pos = off + __popcll(m & ((1ull << t) - 1ull));
-        tv[pos] = kv;
-        ti[pos] = (ki << 8) | kj;
-      }
-      off += __popcll(m);
-    }
-    if (t == 0) ntaps = off;
-  }
+  if (t < 64) list_taps(d.taps + (long long)(d.tap_idx ? d.tap_idx[img] : img) * K2, k, t, tv, ti, &ntaps);
   // the blur input of the tile and its halo: rows y0 - anc .. y0 + th + k - 2 -
   // anc, columns likewise, each at its reflected source element
   const int pw = tw + k - 1, nr = th + k - 1, rowb = pw * C;
@@ -492,17 +527,208 @@ __global__ __launch_bounds__(256) void rdist_tile_kernel(RdArgs a) {
   const int nt = ntaps;
   for (int i = t; i < th * tw; i += 256) {
     const int ly = i / tw, lx = i - ly * tw;
-    const Pix *base = simg + ly * pw + lx;
     float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int u = 0; u < nt; ++u) {
-      const int ij = ti[u];
-      const float w = tv[u];
-      const uint32_t px = base[(ij >> 8) * pw + (ij & 255)];
-#pragma unroll
-      for (int c = 0; c < C; ++c) s[c] = s[c] + w * (float)((px >> (8 * c)) & 255u);
-    }
+    tap_sum<C>(simg + ly * pw + lx, pw, nt, tv, ti, s);
     const long long le = ((long long)(y0 + ly) * r.w + (x0 + lx)) * C;
     blur_store(d, p, eb + le, dst + le, s);
+  }
+}
+
+// --------------------------------------- single distortions, ragged ----
+// The offline generators 02_gen_noise.py, 03_gen_blur.py and 04_gen_fog.py as
+// they spell their arithmetic -- which is not 14's -- and 13:33-56's three
+// steps, one kind per call for a whole ragged batch at native size:
+//   noise 02:18-26: fp64 from image / 255, clip(x + nz, low, 1) * 255, then
+//     np.uint8: truncation toward zero and a wrap modulo 256 (-3.7 -> 253).
+//     02:21's `out.min() < 0` picks low = -1 or 0, but when no element is
+//     negative the lower clip is inert either way, so clip(out, -1, 1) IS the
+//     reference's result for every image: no reduction.  13:37 clips at 0:
+//     the caller's `b`.
+//   fog 04:17-30 / 13:50-56: clip((x * t + A (1 - t)) * 255, 0, 255) in fp64.
+//   blur 03:17-30 / 13:40-48: filter2D of the raw bytes (rdist_tile_kernel's
+//     tap sum on a staged tile), and with `stretch` 03:29's cv2.normalize(...,
+//     0, 255, NORM_MINMAX) behind it: the minimum and maximum of the blurred
+//     bytes of the WHOLE image over all channels, scale and shift in fp64,
+//     convertTo's saturate(rintf(v * (float)scale + (float)shift)).
+// Launches: rsingle_prologue_kernel (elem_base), one tile kernel, and for the
+// blur rsingle_stretch_kernel on the same grid.  The blur kernel leaves one
+// (min, max) record per tile it computed in the workspace; a stretch workgroup
+// reduces the records of its image's own tiles -- counted from the record's h
+// and w, so only what this call wrote is read and the workspace needs no
+// initialisation -- and rescales its tile of `out` in place.  Integer min and
+// max: no order, no atomics.
+struct RsRange { int lo, hi; };
+struct RsArgs {
+  int n, kind, max_h, max_w;
+  const uint8_t *in;
+  uint8_t *out;
+  const rr_single_param *prm;
+  const float *taps;                    // [n][RR_DISTORT_KMAX^2], blur
+  const double *noise;                  // packed in elem_base order, or null -> Philox
+  unsigned long long seed;
+  const rr_ragged_image *tab;
+  long long in_bytes;
+  long long *elem_base;                 // [n], workspace
+  RsRange *range;                       // [n][tiles_y * tiles_x], workspace
+  int tiles_y, tiles_x;                 // tiles of a max_h x max_w image
+};
+constexpr int RS_T = 32;                // the tile side
+
+__device__ __forceinline__ bool rs_valid(const rr_ragged_image &r, const rr_single_param &p, int kind, int c,
+                                         int max_h, int max_w, long long in_bytes) {
+  if (kind == RR_SINGLE_BLUR && (p.ksize < 1 || p.ksize > RR_DISTORT_KMAX)) return false;
+  return rg_valid(r, c, max_h, max_w, in_bytes);
+}
+
+// a workgroup's image and tile: false for an invalid record or a tile outside
+// its image (uniform over the workgroup: return before any barrier)
+struct RsTile { int img, y0, x0, th, tw; };
+__device__ __forceinline__ bool rs_tile(const RsArgs &a, int c, const rr_ragged_image &r, const rr_single_param &p,
+                                        RsTile *q) {
+  q->y0 = ((blockIdx.x % (a.tiles_y * a.tiles_x)) / a.tiles_x) * RS_T;
+  q->x0 = ((blockIdx.x % (a.tiles_y * a.tiles_x)) % a.tiles_x) * RS_T;
+  if (!rs_valid(r, p, a.kind, c, a.max_h, a.max_w, a.in_bytes) || q->y0 >= r.h || q->x0 >= r.w) return false;
+  q->th = r.h - q->y0 < RS_T ? r.h - q->y0 : RS_T;
+  q->tw = r.w - q->x0 < RS_T ? r.w - q->x0 : RS_T;
+  return true;
+}
+
+// min / max over the workgroup's 256 threads: a wave butterfly, the four waves
+// through LDS; every thread gets the result (red: 8 ints, one barrier)
+__device__ __forceinline__ void rs_group_range(int &lo, int &hi, int *red) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const int l = __shfl_xor(lo, o, 64), h = __shfl_xor(hi, o, 64);
+    lo = l < lo ? l : lo;
+    hi = h > hi ? h : hi;
+  }
+  const int t = threadIdx.x;
+  if ((t & 63) == 0) {
+    red[t >> 6] = lo;
+    red[4 + (t >> 6)] = hi;
+  }
+  __syncthreads();
+  for (int u = 0; u < 4; ++u) {
+    lo = red[u] < lo ? red[u] : lo;
+    hi = red[4 + u] > hi ? red[4 + u] : hi;
+  }
+}
+
+__global__ __launch_bounds__(256) void rsingle_prologue_kernel(RsArgs a, int c) {
+  elem_base_scan(a.n, a.elem_base, [&](int i) -> long long {
+    const rr_ragged_image r = a.tab[i];
+    return rs_valid(r, a.prm[i], a.kind, c, a.max_h, a.max_w, a.in_bytes) ? (long long)r.h * r.w * c : 0;
+  });
+}
+
+// noise and fog: per element, the tile's bytes row by row
+template <int KIND>
+__global__ __launch_bounds__(256) void rsingle_point_kernel(RsArgs a, int c) {
+#pragma clang fp contract(off)
+  const int img = blockIdx.x / (a.tiles_y * a.tiles_x);
+  const rr_ragged_image r = a.tab[img];
+  const rr_single_param p = a.prm[img];
+  RsTile q;
+  if (!rs_tile(a, c, r, p, &q)) return;
+  const long long eb = a.elem_base[img];
+  const uint8_t *src = a.in + r.offset;
+  uint8_t *dst = a.out + r.offset;
+  const int rowb = q.tw * c;
+  for (int i = threadIdx.x; i < q.th * rowb; i += 256) {
+    const int ly = i / rowb;
+    const long long le = ((long long)(q.y0 + ly) * r.w + q.x0) * c + (i - ly * rowb);
+    const double x = (double)src[le] / 255.0;
+    if (KIND == RR_SINGLE_NOISE) {
+      const double nz = a.noise ? a.noise[eb + le] : p.a * philox_normal(a.seed, (unsigned long long)(eb + le));
+      double v = x + nz;
+      v = v < p.b ? p.b : (v > 1.0 ? 1.0 : v);               // np.clip(out, low_clip, 1.0)
+      dst[le] = (uint8_t)(int)(v * 255.0);                   // np.uint8: toward zero, then modulo 256
+    } else {
+      dst[le] = trunc_u8((x * p.a + p.b) * 255.0);
+    }
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void rsingle_blur_kernel(RsArgs a) {
+#pragma clang fp contract(off)
+  constexpr int K2 = RR_DISTORT_KMAX * RR_DISTORT_KMAX;
+  constexpr int PS = TilePix<C>::PS;
+  using Pix = typename TilePix<C>::type;
+  __shared__ Pix simg[(RS_T + RR_DISTORT_KMAX - 1) * (RS_T + RR_DISTORT_KMAX - 1)];
+  __shared__ float tv[K2];
+  __shared__ int ti[K2];
+  __shared__ int ntaps;
+  __shared__ int red[8];
+  const int t = threadIdx.x;
+  const int img = blockIdx.x / (a.tiles_y * a.tiles_x);
+  const rr_ragged_image r = a.tab[img];
+  const rr_single_param p = a.prm[img];
+  RsTile q;
+  if (!rs_tile(a, C, r, p, &q)) return;
+  const uint8_t *src = a.in + r.offset;
+  uint8_t *dst = a.out + r.offset;
+  const int k = p.ksize, anc = k / 2;
+  if (t < 64) list_taps(a.taps + (long long)img * K2, k, t, tv, ti, &ntaps);
+  // the raw source bytes of the tile and its halo, each at its reflected place
+  const int pw = q.tw + k - 1, nr = q.th + k - 1, rowb = pw * C;
+  for (int e = t; e < nr * rowb; e += 256) {
+    const int ry = e / rowb, rest = e - ry * rowb;
+    const int cx = rest / C, ch = rest - cx * C;
+    const int yy = reflect101(q.y0 - anc + ry, r.h), xx = reflect101(q.x0 - anc + cx, r.w);
+    ((uint8_t *)simg)[(ry * pw + cx) * PS + ch] = src[((long long)yy * r.w + xx) * C + ch];
+  }
+  __syncthreads();
+  const int nt = ntaps;
+  int lo = 255, hi = 0;
+  for (int i = t; i < q.th * q.tw; i += 256) {
+    const int ly = i / q.tw, lx = i - ly * q.tw;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    tap_sum<C>(simg + ly * pw + lx, pw, nt, tv, ti, s);
+    const long long le = ((long long)(q.y0 + ly) * r.w + (q.x0 + lx)) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      float v = rintf(s[c]);                                 // saturate_cast<uchar>: cvRound
+      v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+      const int b = (int)v;
+      dst[le + c] = (uint8_t)b;
+      lo = b < lo ? b : lo;
+      hi = b > hi ? b : hi;
+    }
+  }
+  if (!p.stretch) return;                                    // uniform
+  rs_group_range(lo, hi, red);
+  if (t == 0) a.range[blockIdx.x] = RsRange{lo, hi};
+}
+
+// 03:29 behind the blur: cv2.normalize(blurred, blurred, 0, 255, NORM_MINMAX)
+__global__ __launch_bounds__(256) void rsingle_stretch_kernel(RsArgs a, int c) {
+#pragma clang fp contract(off)
+  __shared__ int red[8];
+  const int tiles = a.tiles_y * a.tiles_x, img = blockIdx.x / tiles;
+  const rr_ragged_image r = a.tab[img];
+  const rr_single_param p = a.prm[img];
+  RsTile q;
+  if (!p.stretch || !rs_tile(a, c, r, p, &q)) return;
+  const int ny = (r.h - 1) / RS_T + 1, nx = (r.w - 1) / RS_T + 1;   // the image's own tiles
+  const RsRange *rec = a.range + (long long)img * tiles;
+  int lo = 255, hi = 0;
+  for (int j = threadIdx.x; j < ny * nx; j += 256) {
+    const RsRange g = rec[(j / nx) * a.tiles_x + j % nx];
+    lo = g.lo < lo ? g.lo : lo;
+    hi = g.hi > hi ? g.hi : hi;
+  }
+  rs_group_range(lo, hi, red);
+  const double span = (double)(hi - lo);
+  const double scale = 255.0 * (span > DBL_EPSILON ? 1.0 / span : 0.0), shift = 0.0 - (double)lo * scale;
+  const float fs = (float)scale, fb = (float)shift;          // convertTo works in fp32
+  uint8_t *dst = a.out + r.offset;
+  const int rowb = q.tw * c;
+  for (int i = threadIdx.x; i < q.th * rowb; i += 256) {
+    const int ly = i / rowb;
+    const long long le = ((long long)(q.y0 + ly) * r.w + q.x0) * c + (i - ly * rowb);
+    float v = rintf((float)dst[le] * fs + fb);
+    v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+    dst[le] = (uint8_t)(int)v;
   }
 }
 
@@ -588,6 +814,19 @@ static int rd_run(bool draw, int n, int c, int mode, int max_h, int max_w, const
                      prm_out, idx_out, nseed);
   RR_CHECK_LAUNCH();
   return rd_launch(a, c, max_h, max_w, rr_path_read().rdist_tile, st);
+}
+
+// workspace of rr_distort_single_ragged_u8: elem_base[n], then one RsRange per
+// (image, tile of a max_h x max_w image); *groups: the workgroups of the tile
+// grid, which is the launch's limit
+static int rs_plan(int n, int c, int max_h, int max_w, size_t *off_range, size_t *total, long long *groups) {
+  if (n <= 0 || c < 1 || c > 4 || max_h < 1 || max_w < 1) return RR_EINVAL;
+  const long long tiles = (long long)((max_h - 1) / RS_T + 1) * ((max_w - 1) / RS_T + 1);
+  if (tiles > ((1LL << 31) - 1) / n) return RR_EUNSUPPORTED;
+  *groups = tiles * n;
+  *off_range = al16((size_t)n * sizeof(long long));
+  *total = *off_range + (size_t)*groups * sizeof(RsRange);
+  return RR_OK;
 }
 
 }  // namespace
@@ -729,3 +968,45 @@ extern "C" int rr_distort_random_ragged_draws(int n, int c, int max_h, int max_w
   return draw_offsets(p, prm_off, idx_off, seed_off);
 }
 
+// ------------------------------------------ single distortions: C ABI ----
+extern "C" size_t rr_distort_single_ragged_workspace(int n, int c, int max_h, int max_w) {
+  size_t off, total;
+  long long groups;
+  return rs_plan(n, c, max_h, max_w, &off, &total, &groups) == RR_OK ? total : 0;
+}
+
+extern "C" int rr_distort_single_ragged_u8(int n, int c, int kind, int max_h, int max_w, const uint8_t *in,
+                                           size_t in_bytes, const rr_ragged_image *images_dev, uint8_t *out,
+                                           const rr_single_param *params, const float *taps, const double *noise,
+                                           unsigned long long seed, void *ws, size_t ws_bytes, rr_stream stream) {
+  size_t off, total;
+  long long groups;
+  if (!in || !images_dev || !out || !params || !ws || in == out) return RR_EINVAL;   // halo reads: not in place
+  if (kind != RR_SINGLE_NOISE && kind != RR_SINGLE_BLUR && kind != RR_SINGLE_FOG) return RR_EINVAL;
+  if ((kind == RR_SINGLE_BLUR && !taps) || !rg_bytes_ok(in_bytes)) return RR_EINVAL;
+  if (const int rc = rs_plan(n, c, max_h, max_w, &off, &total, &groups)) return rc;
+  if (ws_bytes < total) return RR_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  RsArgs a{n, kind, max_h, max_w, in, out, params, taps, noise, seed, images_dev, (long long)in_bytes,
+           (long long *)ws, (RsRange *)((char *)ws + off), (max_h - 1) / RS_T + 1, (max_w - 1) / RS_T + 1};
+  const dim3 grid((unsigned)groups), block(256);
+  hipLaunchKernelGGL(rsingle_prologue_kernel, dim3(1), block, 0, st, a, c);
+  RR_CHECK_LAUNCH();
+  if (kind == RR_SINGLE_NOISE) {
+    hipLaunchKernelGGL(rsingle_point_kernel<RR_SINGLE_NOISE>, grid, block, 0, st, a, c);
+  } else if (kind == RR_SINGLE_FOG) {
+    hipLaunchKernelGGL(rsingle_point_kernel<RR_SINGLE_FOG>, grid, block, 0, st, a, c);
+  } else {
+    const int rc = rr_dispatch_int<1, 2, 3, 4>(c, [&](auto cc) {
+      hipLaunchKernelGGL(rsingle_blur_kernel<decltype(cc)::value>, grid, block, 0, st, a);
+      RR_CHECK_LAUNCH();
+      return RR_OK;
+    });
+    if (rc) return rc;
+    // the images with `stretch` are known on the device only: the launch is
+    // made whatever the table says, and a workgroup without one leaves at once
+    hipLaunchKernelGGL(rsingle_stretch_kernel, grid, block, 0, st, a, c);
+  }
+  RR_CHECK_LAUNCH();
+  return RR_OK;
+}

@@ -66,6 +66,10 @@ class DistortParam(C.Structure):
                 ("flags", C.c_int32), ("ksize", C.c_int32)]
 
 
+class SingleParam(C.Structure):             # mirrors rr_single_param
+    _fields_ = [("a", C.c_double), ("b", C.c_double), ("ksize", C.c_int32), ("stretch", C.c_int32)]
+
+
 class RaggedImage(C.Structure):             # mirrors rr_ragged_image
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
 
@@ -113,6 +117,7 @@ class PackJob(C.Structure):
 
 RR_DISTORT_FOG, RR_DISTORT_NOISE, RR_DISTORT_BLUR = 1, 2, 4
 RR_DISTORT_KMAX = 15
+RR_SINGLE_NOISE, RR_SINGLE_BLUR, RR_SINGLE_FOG = 0, 1, 2
 
 P_ = C.c_void_p
 I_ = C.c_int
@@ -242,6 +247,9 @@ _SIGS = {
                                          P_]),
     "rr_distort_random_ragged_draws": (I_, [I_, I_, I_, I_, P_, C.POINTER(S_), C.POINTER(S_),
                                             C.POINTER(S_)]),
+    "rr_distort_single_ragged_workspace": (S_, [I_, I_, I_, I_]),
+    "rr_distort_single_ragged_u8": (I_, [I_, I_, I_, I_, I_, P_, S_, P_, P_, P_, P_, P_, C.c_ulonglong, P_, S_,
+                                         P_]),
     "rr_linear_wgrad": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, I_, P_]),
     "rr_linear_dgrad": (I_, [I_, I_, I_, I_, P_, P_, P_, P_, P_]),
     "rr_dropout_fwd": (I_, [L_, F_, C.c_ulonglong, P_, P_, P_, P_, P_]),

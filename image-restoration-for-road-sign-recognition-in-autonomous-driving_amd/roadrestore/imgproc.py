@@ -35,6 +35,13 @@ DataLoader workers and in the inference loop).  Here they take a whole
   resize, as the reference does; ``apply_random_distortions``,
   ``apply_compound_distortion`` and ``RandomDistortion`` take a ``RaggedBatch``
   for that (two launches per batch, the blur input kept on chip).
+* ``add_gaussian_noise`` / ``apply_motion_blur`` / ``add_fog`` -- the offline
+  generators 02:12-27, 03:11-30 and 04:12-31 in THEIR arithmetic (fp64, the
+  uint8 wrap of the noise, the per-image min-max stretch of the blur), which
+  is not 14's; with ``low_clip=0`` / ``normalize=False`` / ``jitter=False``
+  the three steps of 13:33-56.  ``SingleDistortionDataset`` makes the Noise,
+  Blur or Fog pairs 07 trains on without the disk sets, ``PairedDataset`` is
+  07:35-72 over sets that are on disk, ``write_ppm`` writes one.
 """
 from __future__ import annotations
 
@@ -49,14 +56,16 @@ import torch
 
 from . import ops
 from ._lib import (PNG_REASON, RR_DISTORT_BLUR, RR_DISTORT_FOG, RR_DISTORT_KMAX, RR_DISTORT_NOISE,
-                   RR_EUNSUPPORTED, DistortParam, PngImage, PngInfo, RaggedImage, lib)
+                   RR_EUNSUPPORTED, RR_SINGLE_BLUR, RR_SINGLE_FOG, RR_SINGLE_NOISE, DistortParam, PngImage, PngInfo,
+                   RaggedImage, SingleParam, lib)
 
 __all__ = ["Resize", "ToTensor", "Normalize", "Compose", "apply_random_distortions",
            "encode_png", "write_png",
            "RandomDistortion", "motion_blur_table", "DynamicDistortionDataset",
            "apply_compound_distortion", "distortion_params", "psnr", "ssim", "cv_resize",
            "restoration_quality", "RaggedBatch", "read_ppm", "read_png", "read_images", "ImageFolder", "find_images",
-           "IMAGENET_MEAN", "IMAGENET_STD"]
+           "add_gaussian_noise", "apply_motion_blur", "add_fog", "fog_transmissions", "SingleDistortionDataset",
+           "PairedDataset", "write_ppm", "IMAGENET_MEAN", "IMAGENET_STD"]
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)      # 18:31
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -742,6 +751,227 @@ class DynamicDistortionDataset:
 
     def last_draws(self):
         return self._distort.last_draws()
+
+
+# ---------------------------------------------------------------------------
+# the single distortions of the offline generators 02-04 (the sets 07's three
+# SimpleUNet restorers train on) and of 13:33-56, in their own arithmetic
+
+def _as_ragged(x):
+    """a [n, h, w, c] uint8 device tensor as the RaggedBatch of n equal images
+    over the same bytes (no dense kernels: a uniform table) -> (batch, shape or
+    None for a RaggedBatch)"""
+    if isinstance(x, RaggedBatch):
+        ops._need_cuda(x.data)
+        return x, None
+    _check_u8(x)
+    ops._need_cuda(x)
+    n, h, w, c = x.shape
+    if n * h * w * c == 0:
+        raise ValueError(f"empty batch {tuple(x.shape)}")
+    rec = np.zeros(n, dtype=_RECORD)
+    rec["offset"] = np.arange(n, dtype=np.int64) * (h * w * c)
+    rec["h"], rec["w"] = h, w
+    return RaggedBatch(x.contiguous().view(-1), rec, c), tuple(x.shape)
+
+
+def _single(x, kind, params, taps=None, noise=None, seed=0):
+    b, shape = _as_ragged(x)
+    if noise is not None:
+        noise = noise.reshape(-1)
+    y = ops.distort_single_ragged_u8(b.data, b.table, b.max_hw, b.channels, kind, params, taps=taps,
+                                     noise=noise, seed=seed)
+    return b.with_data(y) if shape is None else y.view(shape)
+
+
+def add_gaussian_noise(x, var=0.01, low_clip=-1.0, seed=None, noise=None):
+    """02_gen_noise.py:12-27 on a [n, h, w, c] uint8 device batch or a
+    RaggedBatch (-> the same kind): ``clip(image / 255 + N(0, var), low_clip,
+    1) * 255`` in fp64, then ``np.uint8``, which truncates toward zero and
+    wraps the negatives modulo 256 -- the Noise set carries that.
+    ``low_clip=-1.0`` is 02:21-25 for every image (its branch is inert when no
+    element is negative); ``low_clip=0.0`` is 13:33-38.  The field is drawn on
+    the device (Philox4x32-10 keyed by ``seed``, drawn from ``random`` when
+    None, and the packed element index) unless ``noise`` gives it: fp64, the
+    reference's ``np.random.normal(0, var ** 0.5, shape)``, in packed element
+    order."""
+    n = len(x) if isinstance(x, RaggedBatch) else x.shape[0]
+    if seed is None:
+        seed = _random.getrandbits(64)
+    p = SingleParam(float(var) ** 0.5, float(low_clip), 0, 0)
+    return _single(x, RR_SINGLE_NOISE, [p] * n, noise=noise, seed=seed)
+
+
+def apply_motion_blur(x, degree=10, angle=45, normalize=True):
+    """03_gen_blur.py:11-30: ``cv2.filter2D`` with the rotated line kernel,
+    then ``cv2.normalize(blurred, blurred, 0, 255, NORM_MINMAX)`` (03:29),
+    which stretches every image's own range, taken over all channels, to
+    0..255 -- a flat image comes out black.  ``normalize=False`` is 13:40-48.
+    ``degree`` is the kernel's side, at most RR_DISTORT_KMAX."""
+    n = len(x) if isinstance(x, RaggedBatch) else x.shape[0]
+    taps = ops.motion_blur_kernel(degree, angle).unsqueeze(0).expand(n, -1, -1).contiguous()
+    p = SingleParam(0.0, 0.0, int(degree), 1 if normalize else 0)
+    return _single(x, RR_SINGLE_BLUR, [p] * n, taps=taps)
+
+
+def fog_transmissions(n, fog_intensity=0.8, rng=None, jitter=True):
+    """the n values of t that add_fog uses: 04:24-25, one ``rng.uniform(0.8,
+    1.2)`` per image in batch order and the clip to [0.1, 0.9]; without
+    ``jitter`` 13:54's ``1 - fog_intensity``, unclipped"""
+    rng = rng or _random
+    if not jitter:
+        return [1.0 - fog_intensity] * n
+    return [min(max(1.0 - fog_intensity * rng.uniform(0.8, 1.2), 0.1), 0.9) for _ in range(n)]
+
+
+def add_fog(x, fog_intensity=0.8, rng=None, jitter=True):
+    """04_gen_fog.py:12-31: ``clip((image / 255 * t + A (1 - t)) * 255, 0,
+    255)`` truncated, in fp64, A = 0.9, t drawn per image as 04:24-25 draws it
+    (``fog_transmissions``: Python's ``random``, or ``rng``);
+    ``jitter=False`` is 13:50-56's fixed t."""
+    n = len(x) if isinstance(x, RaggedBatch) else x.shape[0]
+    A = 0.9
+    params = [SingleParam(t, A * (1 - t), 0, 0) for t in fog_transmissions(n, fog_intensity, rng, jitter)]
+    return _single(x, RR_SINGLE_FOG, params)
+
+
+def _device_or_default(device):
+    return torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+
+
+def _batches(n, batch_size, shuffle, generator, load):
+    order = torch.randperm(n, generator=generator).tolist() if shuffle else list(range(n))
+    for a in range(0, n, int(batch_size)):
+        yield load(order[a:a + int(batch_size)])
+
+
+class SingleDistortionDataset:
+    """What 02 / 03 / 04 write to disk and 07 reads back, made on the device
+    instead: ``task`` is 'Noise' (02:44: var 0.02), 'Blur' (03:41: degree 12,
+    angle 45, with the stretch) or 'Fog' (04:42: intensity 0.8).  The file
+    list is DynamicDistortionDataset's (``sorted(clean_root.glob('*/*.ppm'))``);
+    ``load(indices)`` reads the files with one ``read_ppm``, distorts the
+    batch at native size and puts both through ``transform`` -> ``(bad,
+    clean)``, 07:72's order; ``batches(batch_size, shuffle, generator)``
+    yields that for one pass, the last batch short.  The noise seeds and the
+    fog draws come from an owned ``random.Random(seed)``.  The constructor
+    lists files only and touches no device."""
+
+    TASKS = ("Noise", "Blur", "Fog")
+
+    def __init__(self, clean_root, task, transform=None, device=None, seed=0, threads=0):
+        if task not in self.TASKS:
+            raise ValueError(f"task {task!r}: one of {self.TASKS}")
+        self.clean_files = sorted(Path(clean_root).glob('*/*.ppm'))
+        self.task = task
+        self.transform = transform
+        self.device = device
+        self.threads = threads
+        self.rng = _random.Random(seed)
+
+    def __len__(self):
+        return len(self.clean_files)
+
+    def distort(self, clean):
+        if self.task == "Noise":
+            return add_gaussian_noise(clean, var=0.02, seed=self.rng.getrandbits(64))
+        if self.task == "Blur":
+            return apply_motion_blur(clean, degree=12, angle=45)
+        return add_fog(clean, fog_intensity=0.8, rng=self.rng)
+
+    def load(self, indices):
+        clean = read_ppm([self.clean_files[int(i)] for i in indices], _device_or_default(self.device),
+                         self.threads)
+        bad = self.distort(clean)
+        if self.transform is not None:
+            bad, clean = self.transform(bad), self.transform(clean)
+        return bad, clean
+
+    def batches(self, batch_size, shuffle=False, generator=None):
+        return _batches(len(self.clean_files), batch_size, shuffle, generator, self.load)
+
+
+class PairedDataset:
+    """07_train_restoration.py:35-72 from disk, in device batches.
+    ``data_pairs`` is built as 07:42-55 builds it: the clean files are
+    ``sorted(clean_root.glob('*/*.ppm'))``, the distorted file has the same
+    relative path under ``distorted_root``, with the suffix ``.png`` only if
+    that does not exist, and a clean file without either is dropped.
+    ``load(indices)`` reads both sides with ``read_images`` and puts them
+    through ``transform`` -> ``(bad, clean)`` (07:72); ``batches`` as
+    SingleDistortionDataset's.  The constructor touches no device."""
+
+    def __init__(self, clean_root, distorted_root, transform=None, device=None, threads=0):
+        self.clean_root = Path(clean_root)
+        self.distorted_root = Path(distorted_root)
+        self.transform = transform
+        self.device = device
+        self.threads = threads
+        self.clean_files = sorted(self.clean_root.glob('*/*.ppm'))
+        self.data_pairs = []
+        for c_path in self.clean_files:
+            d_path = self.distorted_root / c_path.relative_to(self.clean_root)
+            if not d_path.exists():
+                d_path = d_path.with_suffix('.png')
+            if d_path.exists():
+                self.data_pairs.append((d_path, c_path))
+
+    def __len__(self):
+        return len(self.data_pairs)
+
+    def load(self, indices):
+        device = _device_or_default(self.device)
+        pairs = [self.data_pairs[int(i)] for i in indices]
+        bad = read_images([d for d, _ in pairs], device, self.threads)
+        clean = read_images([c for _, c in pairs], device, self.threads)
+        if self.transform is not None:
+            bad, clean = self.transform(bad), self.transform(clean)
+        return bad, clean
+
+    def batches(self, batch_size, shuffle=False, generator=None):
+        return _batches(len(self.data_pairs), batch_size, shuffle, generator, self.load)
+
+
+def write_ppm(images, paths, threads=0):
+    """Binary PPM writer (P6, maxval 255: the header ``cv2.imwrite`` writes to
+    a ``.ppm`` path, so a set lands where 02:54, 03:46 and 04:47 write it) for
+    an [n, h, w, 3] uint8 batch or a 3-channel RaggedBatch, device or host.
+    One D2H copy of the whole buffer, then ``threads`` host threads (0 = up to
+    8) write the files; parent directories are created.  ``read_ppm`` reads
+    the files back byte for byte.  The bytes are written as they lie: the
+    files hold the batch's channel order."""
+    paths = [os.fspath(p) for p in paths]
+    if isinstance(images, RaggedBatch):
+        if images.channels != 3:
+            raise ValueError(f"write_ppm: {images.channels} channels (a PPM holds 3)")
+        host = images.data.cpu().numpy()
+        recs = [(int(o), int(h), int(w)) for o, h, w in images.records]
+    else:
+        if (not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() != 4
+                or images.shape[-1] != 3):
+            raise ValueError("write_ppm: expected an [n, h, w, 3] uint8 tensor or a RaggedBatch")
+        n, h, w, _ = images.shape
+        host = images.contiguous().cpu().numpy().reshape(-1)
+        recs = [(i * h * w * 3, h, w) for i in range(n)]
+    if len(paths) != len(recs):
+        raise ValueError(f"{len(recs)} images, {len(paths)} paths")
+    for d in {os.path.dirname(p) for p in paths}:
+        if d:
+            os.makedirs(d, exist_ok=True)
+
+    def one(i):
+        o, h, w = recs[i]
+        with open(paths[i], "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (w, h))
+            f.write(memoryview(host[o:o + h * w * 3]))
+
+    workers = int(threads) if threads else min(8, len(recs))
+    if workers <= 1:
+        for i in range(len(recs)):
+            one(i)
+    else:
+        with ThreadPoolExecutor(workers) as pool:
+            list(pool.map(one, range(len(recs))))
 
 
 def cv_resize(x, size):

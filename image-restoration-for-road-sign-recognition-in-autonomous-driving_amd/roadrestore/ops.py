@@ -13,7 +13,8 @@ import ctypes as C
 import torch
 
 from ._lib import (path_flag, RR_ACT_NOFULL, RR_ACT_POOL, RR_ACT_PRELU, RR_ACT_RES, RR_BF16, RR_F32, RR_CONV1X1, RR_CONV3X3,
-                   RR_CONVT_DOWN, RR_CONVT_UP, RR_DISTORT_KMAX, RR_EUNSUPPORTED, BnBwdDesc, DistortParam, IgemmDesc, PackJob, WgradDesc, lib)
+                   RR_CONVT_DOWN, RR_CONVT_UP, RR_DISTORT_KMAX, RR_EUNSUPPORTED, RR_SINGLE_BLUR, RR_SINGLE_FOG, RR_SINGLE_NOISE,
+                   BnBwdDesc, DistortParam, IgemmDesc, PackJob, SingleParam, WgradDesc, lib)
 
 __all__ = [
     "rr_dtype", "stream", "pack_conv", "pack_convT", "bias_tile4", "igemm", "wgrad",
@@ -26,7 +27,8 @@ __all__ = [
     "nearest_resize_bwd", "fold_conv_bn", "bn_stats", "linear_wgrad", "linear_dgrad",
     "dropout_fwd", "dropout_bwd", "dropout_mask", "cross_entropy", "softmax_max", "sgd_",
     "resize_ragged_u8", "png_unfilter", "distort_ragged_u8", "cv_resize_ragged_u8", "eval_ragged_u8",
-    "cv_resize_linear_u8", "distort_random_u8", "distort_random_ragged_u8",
+    "cv_resize_linear_u8", "distort_random_u8", "distort_random_ragged_u8", "distort_single_ragged_u8",
+    "single_workspace",
 ]
 
 
@@ -1437,6 +1439,66 @@ def distort_random_ragged_u8(data, table, max_hw, c, seed, step, blur_table, ws=
     L.check(L.rr_distort_random_ragged_u8(n, c, max_h, max_w, _p(data), data.numel(), _p(table), _p(out),
                                           int(seed) & (2 ** 64 - 1), _p(step), _p(blur_table), _p(ws),
                                           ws.numel(), stream()), "rr_distort_random_ragged_u8")
+    return out
+
+
+def single_workspace(n, c, max_hw):
+    """bytes rr_distort_single_ragged_u8 needs for n images of c channels bounded by ``max_hw``"""
+    wsb = lib().rr_distort_single_ragged_workspace(int(n), int(c), int(max_hw[0]), int(max_hw[1]))
+    if wsb == 0:
+        raise RuntimeError(f"rr_distort_single_ragged_u8: unsupported batch n={n} c={c} max={tuple(max_hw)}")
+    return wsb
+
+
+def distort_single_ragged_u8(data, table, max_hw, c, kind, params, taps=None, noise=None, seed=0, out=None,
+                             ws=None):
+    """One of the offline generators' distortions (``kind``: RR_SINGLE_NOISE
+    02:18-26 / 13:33-38, RR_SINGLE_BLUR 03:17-30 / 13:40-48, RR_SINGLE_FOG
+    04:17-30 / 13:50-56) on n images of unequal size, each at its native size.
+    ``data`` / ``table`` / ``max_hw`` / ``c`` / ``out``: as distort_ragged_u8;
+    ``params``: a list of n SingleParam, or their bytes already on the device
+    (uint8 [n, 24]: a captured call); ``taps``: [n, KMAX, KMAX] fp32 (host or
+    device), the blur only; ``noise``: an optional 1-D fp64 field, already
+    scaled, in packed element order, else Philox(seed) keyed by that index;
+    ``ws``: single_workspace bytes (a caller that replays keeps its own).  An
+    invalid record, or a blur with ksize outside [1, KMAX], is skipped:
+    nothing read, nothing written."""
+    n, c, kind = _ragged_tensors("distort_single_ragged_u8", data, table, out, ws), int(c), int(kind)
+    max_h, max_w = int(max_hw[0]), int(max_hw[1])
+    if kind not in (RR_SINGLE_NOISE, RR_SINGLE_BLUR, RR_SINGLE_FOG):
+        raise ValueError(kind)
+    if isinstance(params, torch.Tensor):
+        _need_cuda(params)
+        if params.dtype != torch.uint8 or tuple(params.shape) != (n, C.sizeof(SingleParam)) or not params.is_contiguous():
+            raise TypeError("params on the device: expected a contiguous uint8 [n, 24] tensor of rr_single_param")
+        prm = params
+    else:
+        if len(params) != n:
+            raise ValueError("one SingleParam per image")
+        prm = torch.frombuffer(bytearray((SingleParam * n)(*params)), dtype=torch.uint8).to(data.device)
+    if kind == RR_SINGLE_BLUR:
+        if taps is None:
+            raise ValueError("the blur needs taps [n, KMAX, KMAX]")
+        taps = _taps_dev(taps, n, data.device)
+    else:
+        taps = None
+    if noise is not None:
+        noise = noise.to(data.device, torch.float64).contiguous()
+        # the elements the library counts (the table is read back: an explicit field is a parity run)
+        t = table.cpu()
+        off, hw = t.view(torch.int64)[:, 0].tolist(), t.view(torch.int32)[:, 2:4].tolist()
+        need = sum(h * w * c for o, (h, w) in zip(off, hw)
+                   if 1 <= h <= max_h and 1 <= w <= max_w and 0 <= o and o + h * w * c <= data.numel())
+        if noise.dim() != 1 or noise.numel() < need:
+            raise ValueError(f"noise must be a 1-D field of the batch's {need} elements in table order")
+    if out is not None and out.data_ptr() == data.data_ptr():
+        raise TypeError("distort_single_ragged_u8 out: not in place")
+    out = _ragged_out("distort_single_ragged_u8", data, out)
+    ws = _ws(single_workspace(n, c, (max_h, max_w)), data.device) if ws is None else ws
+    L = lib()
+    L.check(L.rr_distort_single_ragged_u8(n, c, kind, max_h, max_w, _p(data), data.numel(), _p(table), _p(out),
+                                          _p(prm), _p(taps), _p(noise), int(seed) & (2 ** 64 - 1), _p(ws),
+                                          ws.numel(), stream()), "rr_distort_single_ragged_u8")
     return out
 
 

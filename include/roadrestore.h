@@ -913,6 +913,53 @@ int rr_distort_random_ragged_u8(int n, int c, int max_h, int max_w,
 int rr_distort_random_ragged_draws(int n, int c, int max_h, int max_w, const void *workspace,
                                    size_t *params_off, size_t *index_off, size_t *seed_off);
 
+/* The three single distortions of the offline generators, as THEY spell them
+ * (02_gen_noise.py, 03_gen_blur.py, 04_gen_fog.py: the sets the three
+ * SimpleUNet restorers of 07 train on) and as 13:33-56 spells them -- not
+ * 14's arithmetic -- for a ragged batch at native size.  `kind` holds for the
+ * whole batch, as each script applies one distortion to every file; the
+ * per-image values are read on the device only.
+ *   noise (02:18-26): v = clip(u8 / 255.0 + nz, b, 1.0) * 255.0 in fp64, the
+ *     byte (uint8_t)(int)v: toward zero, then modulo 256, as np.uint8 wraps
+ *     the negatives (-3.7 -> 253).  b = -1.0 gives 02 for every image (when no
+ *     element is negative, 02:21-25's lower clip is inert either way), b = 0.0
+ *     gives 13:37.  nz = noise[e], or a * Philox normal keyed by (seed, e), e
+ *     the element index of rr_distort_ragged_u8 (elem_base order).
+ *   fog (04:17-30, 13:50-56): clip((u8 / 255.0 * a + b) * 255.0, 0, 255)
+ *     truncated, in fp64; a = t, b = A * (1 - t).
+ *   blur (03:17-30, 13:40-48): cv2.filter2D of the source bytes with image
+ *     i's ksize x ksize taps, as rr_distort_u8 computes it; with stretch = 1
+ *     followed by 03:29's cv2.normalize(..., 0, 255, NORM_MINMAX): smin / smax
+ *     over the blurred bytes of the whole image, all channels together, scale
+ *     = 255.0 * (smax - smin > DBL_EPSILON ? 1.0 / (smax - smin) : 0.0), shift
+ *     = -smin * scale in fp64, byte = saturate(rintf(v * (float)scale +
+ *     (float)shift)): a flat image becomes zeros.
+ * The contract is rr_distort_ragged_u8's: `out` as long as `in`, image i at
+ * its own offset, no other byte written; an invalid record (rr_ragged_check,
+ * or blur with ksize outside [1, KMAX]) reads nothing, writes nothing and
+ * counts 0 elements; no float atomics, no host synchronisation, graph-
+ * capturable.  Two launches (prologue + 32 x 32 tiles), three for the blur
+ * (the stretch, which reads only the per-tile ranges the same call wrote: the
+ * workspace needs no initialisation), whatever n is.  Workspace: elem_base[n]
+ * plus one (min, max) record per tile of n max_h x max_w images.
+ * RR_EINVAL: a null required pointer (taps_dev for the blur only), n <= 0, c
+ * outside 1..4, an unknown kind, max_h / max_w < 1, in_bytes == 0, or in ==
+ * out; RR_EUNSUPPORTED (the query: 0): 2^31 tiles or more; RR_EWORKSPACE: a
+ * workspace smaller than the query; all before any launch. */
+enum { RR_SINGLE_NOISE = 0, RR_SINGLE_BLUR = 1, RR_SINGLE_FOG = 2 };
+typedef struct rr_single_param {   /* one per image, device memory */
+  double a;        /* noise: sigma            fog: t                         */
+  double b;        /* noise: low clip (-1.0 as 02:21-25, 0.0 as 13:37)  fog: A*(1-t), formed on the host in fp64 */
+  int32_t ksize;   /* blur: degree, 1..RR_DISTORT_KMAX                       */
+  int32_t stretch; /* blur: 1 = NORM_MINMAX to 0..255 (03:29), 0 = none (13:40-48) */
+} rr_single_param;
+size_t rr_distort_single_ragged_workspace(int n, int c, int max_h, int max_w);
+int rr_distort_single_ragged_u8(int n, int c, int kind, int max_h, int max_w,
+                                const uint8_t *in, size_t in_bytes, const rr_ragged_image *images_dev,
+                                uint8_t *out, const rr_single_param *params_dev, const float *taps_dev,
+                                const double *noise, unsigned long long seed,
+                                void *workspace, size_t workspace_bytes, rr_stream stream);
+
 /* running loss on device: acc[0] += x[0] (fp64), count[0] += 1 -- the
  * reference's per-step `running_loss += loss.item()` (14:246) without a host
  * sync; read acc / count once per epoch */
